@@ -16,6 +16,10 @@ anything in this process touches the GPU, relays rank 0's line and exits with th
 code.  Under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it is a rank.
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs if asked and prints the line.
+Everything else the line can carry -- the other arithmetic variant, the CPU baseline, the accuracy legs,
+live counters under rocprofv3, the block-partition variant of c5 on several GPUs -- runs only with --full.
 """
 from __future__ import annotations
 
@@ -214,6 +218,63 @@ def lean_vs_exact_after_10_cycles(device):
                     "roundings of one history separate like nearby trajectories of any chaotic system -- "
                     "about one decade per cycle, the same rate at which the CPU path's libm and portable "
                     "flavours separate; a history is re-sequenced only where a difference flips a comparison"}
+
+
+DUMP_CELLS = 1 << 20        # --dump-outputs: cells sampled per field
+DUMP_PHOTONS = 1 << 17      # --dump-outputs: photons sampled (by stream id)
+DUMP_SEED = 20250607
+
+
+def dump_outputs(drv, out_dir: str) -> None:
+    """--dump-outputs: what the timed path computed in its last step, as a caller of McblockDriver.Step reads
+    it (this rank's blocks and photons; rank 0's on several GPUs), one float64 .npy per array, ~49 MB in all:
+
+      * tally / edelta / u: the fields a step writes, at a fixed, seeded sample of the owned blocks' interior
+        cells (flat index over [block, k, j, i]: cell_index.npy);
+      * photon_<attribute>: the photons whose stream ids are a fixed, seeded sample of [0, next_id)
+        (photon_id.npy), looked up by id -- the slot order moves with DefragParticles, whose schedule
+        depends on timing; NaN where that photon is not alive here; the 64-bit stream state as two
+        32-bit halves (photon_rng_hi / photon_rng_lo);
+      * totals: [photons alive, sum of w, sum of tally, sum of edelta, sum of u] over everything owned.
+
+    The same arguments give the same inputs in every run, so two builds can be compared file by file."""
+    import torch
+    from jaybenne_amd import _lib
+    md = drv.md
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    rng = np.random.default_rng(DUMP_SEED)
+    torch.cuda.synchronize(md.device)
+    sl = drv.mesh.interior()
+    interior = {k: md.fields[k][:md.nowned][sl].reshape(-1) for k in ("tally", "edelta", "u")}
+    ncell = int(interior["tally"].numel())
+    cells = np.sort(rng.choice(ncell, size=min(DUMP_CELLS, ncell), replace=False))
+    cells_t = torch.from_numpy(cells).to(md.device)
+    save("cell_index", cells)
+    for k, v in interior.items():
+        save(k, v[cells_t].cpu().numpy())
+
+    n = md.n
+    nid = int(md.next_id)
+    want = np.sort(rng.choice(nid, size=min(DUMP_PHOTONS, nid), replace=False)).astype(np.int64)
+    save("photon_id", want)
+    want_t = torch.from_numpy(want).to(md.device)
+    ids = md.swarm["id"][:n]
+    order = torch.argsort(ids)
+    pos = torch.searchsorted(ids[order], want_t).clamp_(max=max(n - 1, 0))
+    found = (ids[order][pos] == want_t) if n > 0 else torch.zeros_like(want_t, dtype=torch.bool)
+    slot = order[pos] if n > 0 else pos
+    for k in _lib.SWARM_F64 + _lib.SWARM_I32:
+        v = md.swarm[k][slot].double() if n > 0 else torch.zeros(len(want), dtype=torch.float64, device=md.device)
+        save(f"photon_{k}", torch.where(found, v, float("nan")).cpu().numpy())
+    r = md.swarm["rng"][slot] if n > 0 else torch.zeros(len(want), dtype=torch.int64, device=md.device)
+    save("photon_rng_hi", torch.where(found, ((r >> 32) & 0xFFFFFFFF).double(), float("nan")).cpu().numpy())
+    save("photon_rng_lo", torch.where(found, (r & 0xFFFFFFFF).double(), float("nan")).cpu().numpy())
+    save("totals", [float(n), float(md.swarm["w"][:n].sum()) if n > 0 else 0.0]
+         + [float(v.sum()) for v in interior.values()])
 
 
 LOG_DIR = os.path.join(ROOT, "gpurun_out", "bench_logs")
@@ -498,6 +559,13 @@ def main() -> None:
                     help="10000000 = BASELINE configs[1] per GPU (default); 12500000 = north_star's "
                          "target invocation (1e8 particles on 8 GPUs)")
     ap.add_argument("--block-nx", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the other arithmetic variant, the "
+                         "CPU baseline, the accuracy legs, live counters (1 GPU) and the block-partition variant "
+                         "of c5 (several GPUs); the --no-* options below switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy "
+                         "(float64, a fixed seeded sample of fields and photons; dump_outputs())")
     ap.add_argument("--cpu-sample", type=int, default=2_500_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--workload", default="c2", choices=["c1", "c2", "c3", "c3-1d", "c4", "c5"],
@@ -525,14 +593,18 @@ def main() -> None:
                     help="several GPUs, c5: skip the extra run on the block partition when 'auto' chose the "
                          "replicated mesh (config.blocks_variant)")
     ap.add_argument("--no-live-counters", action="store_true",
-                    help="do not measure roofline.traffic / valu_issue_frac / fp64_counter_frac with four child runs "
-                         "under rocprofv3 (1 GPU, default line); the line then quotes the committed counter summary, "
-                         "labelled")
+                    help="--full: do not measure roofline.traffic / valu_issue_frac / fp64_counter_frac with four "
+                         "child runs under rocprofv3 (1 GPU); the line then quotes the committed counter summary, "
+                         "labelled, as a plain run's does")
     ap.add_argument("--no-other-variant", action="store_true",
-                    help="skip the one extra step in the other arithmetic variant (profiling runs)")
+                    help="--full: skip the one extra step in the other arithmetic variant")
     ap.add_argument("--arithmetic", choices=("lean", "exact"), default=None,
                     help="arithmetic of the gray IMC tracking step (default: the library's, lean)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         sys.exit(self_launch(args))
@@ -650,6 +722,8 @@ def main() -> None:
     if comm is not None:
         wall = comm.allreduce_max_float(wall)
         histories, events = (int(v) for v in comm.allreduce_sum_int64(np.array([histories, events])))
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(drv, args.dump_outputs)
 
     # the other arithmetic variant of the gray IMC kernel, one step, for the record (1 GPU only;
     # outside the timed region above)
@@ -662,7 +736,7 @@ def main() -> None:
     handoff_records = int(md.handoff_records)
     exchange_s, wait_s = float(md.exchange_seconds), float(md.transport_wait_seconds)
     coll_s = float(md.collective_seconds)
-    if args.gpus == 1 and not md.pkg.Param("use_ddmc") and not args.no_other_variant:
+    if args.full and args.gpus == 1 and not md.pkg.Param("use_ddmc") and not args.no_other_variant:
         kept = list(md.kernel_events)
         mode = md.pkg.arithmetic()
         md.pkg.set_arithmetic("exact" if mode == "lean" else "lean")
@@ -683,8 +757,8 @@ def main() -> None:
     # blocks balances better than 1.23 x the mean) -- SURVEY 8e calls that a cross-check, north_star mandates the
     # block partition with hand-off: run that too, a few steps, and report it beside
     blocks_variant = None
-    if (world > 1 and args.workload == "c5" and args.decomposition == "auto" and drv.decomposition == "replicated"
-            and not args.no_blocks_variant):
+    if (args.full and world > 1 and args.workload == "c5" and args.decomposition == "auto"
+            and drv.decomposition == "replicated" and not args.no_blocks_variant):
         rank_log("the same workload on the block partition (config.blocks_variant)")
         drv_b = mcblock.McblockDriver(make_deck(args.gpus, args.particles_per_gpu, args.block_nx, args.workload),
                                       rank=rank, nranks=world, comm=comm, device=device, capacity_factor=3.0,
@@ -832,8 +906,8 @@ def main() -> None:
                     "alike) divided by the number of launches they cover"}
         roof["traffic_source"] = ((pmc_file + " (rocprofv3 --pmc passes of this command; not measured in this run)")
                                   if pmc else None)
-        if args.gpus == 1 and not args.no_live_counters and not args.no_cpu_baseline:
-            # (the default run: measure them now -- the GPU is idle, the timed region is over)
+        if args.full and args.gpus == 1 and not args.no_live_counters and not args.no_cpu_baseline:
+            # (--full: measure them now -- the GPU is idle, the timed region is over)
             live = live_counters(args)
             if live is not None:
                 roof["traffic"] = live["bytes"]
@@ -932,7 +1006,7 @@ def main() -> None:
         }
         if md.phase_times is not None:
             out["phase_ms_per_step"] = {k: 1e3 * v / args.steps for k, v in md.phase_times.items()}
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.block_nx)
             if not args.no_accuracy:
                 out["accuracy"] = accuracy(device, out["cpu_baseline"]["cores"])

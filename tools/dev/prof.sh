@@ -17,7 +17,7 @@ C4="python3 bench.py --workload c4 --particles-per-gpu 10000000 --steps 1 --warm
 C5="python3 bench.py --workload c5 --particles-per-gpu 10000000 --steps 1 --warmup 0 --no-cpu-baseline"
 C2X="python3 bench.py --arithmetic exact --steps 1 --warmup 0 --no-cpu-baseline --no-other-variant"
 if [ "$PART" != 2 ] && [ "$PART" != pmc ]; then
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -o runc -- python3 bench.py > $O/bench_c2_under_rocprof.json 2> $O/stats_c2.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c2 -o runc -- python3 bench.py --full > $O/bench_c2_under_rocprof.json 2> $O/stats_c2.err
 echo "stats c2 done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_c3 -o runc -- python3 bench.py --workload c3 --particles-per-gpu 100000000 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_c3_under_rocprof.json 2> $O/stats_c3.err
 echo "stats c3 done"
@@ -49,10 +49,10 @@ done
 # configs[4] cycle
 timeout -k 10 300 rocprofv3 --marker-trace --kernel-trace --stats --output-format csv -d $O/markers_c5 -o runc -- python3 bench.py --workload c5 --particles-per-gpu 10000000 --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_c5_markers.json 2> $O/markers_c5.err || echo "marker trace FAILED"
 echo "marker trace done"
-timeout -k 10 400 python3 bench.py > $O/bench_c2.json 2> $O/bench_c2.err
+timeout -k 10 400 python3 bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
 for w in "c1 100000" "c3 100000000" "c3-1d 100000000" "c4 10000000" "c5 10000000"; do
   set -- $w
-  timeout -k 10 300 python3 bench.py --workload $1 --particles-per-gpu $2 --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err
+  timeout -k 10 300 python3 bench.py --full --workload $1 --particles-per-gpu $2 --no-cpu-baseline > $O/bench_$1.json 2> $O/bench_$1.err
   echo "bench $1 done"
 done
 echo all done
