@@ -13,7 +13,10 @@
 //   context's stream), over a jb_exchange_transport: "rccl" = jb_transport_rccl on a communicator this
 //   program bootstraps over MPI (ncclGetUniqueId / ncclCommInitRank: one rank per GPU -- the production
 //   path; the records never leave the device), "mpi" = the same two collectives written with MPI and
-//   host staging below (runs with all ranks on one GPU, which RCCL refuses).
+//   host staging below (runs with all ranks on one GPU, which RCCL refuses);
+// "step": the whole cycle as ONE call of the C++ mirror, jaybenne_amd::RadiationStep(md, t, dt, &transport,
+//   rank, nranks) -> jb_radiation_step_ranks: derived fields, transport, hand-off through jb_exchange over the
+//   MPI transport of "mpi", completion test, compaction, UpdateFluid -- the iterate-sublist inside the library.
 //
 // Problem: inputs/stepdiff.in in 1-D (x in [-0.5, 0.5], sigma_s = 1e3, no absorption, T = 1e5 K
 // for x < 0 and 1 K for x >= 0, reflecting walls), `blocks` meshblocks dealt to the R ranks in
@@ -42,6 +45,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "jaybenne_amd.hpp"
@@ -111,8 +116,10 @@ int main(int argc, char **argv) {
   const int halo_rings = argc > 5 ? std::atoi(argv[5]) : 1;
   const char *dump_prefix = argc > 6 && std::strcmp(argv[6], "-") != 0 ? argv[6] : nullptr;
   const char *exchange = argc > 7 ? argv[7] : "tasks";
-  if (std::strcmp(exchange, "tasks") != 0 && std::strcmp(exchange, "mpi") != 0 && std::strcmp(exchange, "rccl") != 0) {
-    if (rank == 0) std::fprintf(stderr, "exchange must be tasks, mpi or rccl\n");
+  const bool one_step = std::strcmp(exchange, "step") == 0;
+  if (std::strcmp(exchange, "tasks") != 0 && std::strcmp(exchange, "mpi") != 0 && std::strcmp(exchange, "rccl") != 0 &&
+      !one_step) {
+    if (rank == 0) std::fprintf(stderr, "exchange must be tasks, mpi, rccl or step\n");
     MPI_Finalize();
     return 2;
   }
@@ -145,8 +152,15 @@ int main(int argc, char **argv) {
   jb_eos eos{JB_EOS_IDEAL_GAS, 0, 1.66666666667 - 1.0, 1.0 / (1.66666666667 - 1.0)};
   jb_opacity opac{JB_OPAC_GRAY, 0, 0.0, c, sb};
   jb_scattering scat{JB_SCAT_GRAY, 0, 1.0e3, 1.0};
-  jb_context *ctx = nullptr;
-  JB_OK(jb_initialize(&p, &eos, &opac, &scat, device, &ctx));
+  // (the package through the C++ mirror: "step" drives the cycle through its MeshData)
+  std::shared_ptr<jaybenne_amd::StateDescriptor> pkg;
+  try {
+    pkg = jaybenne_amd::Initialize(p, opac, scat, eos, device);
+  } catch (const jaybenne_amd::Error &e) {
+    std::fprintf(stderr, "jaybenne_amd::Initialize failed: %s\n", e.what());
+    MPI_Abort(MPI_COMM_WORLD, 4);
+  }
+  jb_context *ctx = pkg->ctx();
 
   // ---- mesh: blocks [b0, b1) belong to this rank; resident = those + the halo copies
   const int ng = 2;
@@ -211,8 +225,29 @@ int main(int argc, char **argv) {
   v.blk_level = level.data(); v.blk_nbr_lev = nbr_lev.data();
   v.rho = fptr[0].data(); v.sie = fptr[1].data(); v.u = fptr[2].data(); v.fleck = fptr[3].data();
   v.tally = fptr[4].data(); v.edelta = fptr[5].data(); v.src_ew = fptr[6].data(); v.src_num = fptr[7].data();
-  jb_mesh *mesh = nullptr;
-  JB_OK(jb_mesh_create(ctx, &v, &mesh));
+  int32_t *prefix = dev_alloc<int32_t>((size_t)nb * nx);
+  // the pool growth RadiationStep's reserve calls: every array reallocated at twice the need, 0..n-1 kept
+  auto grow = [](jb_swarm_view &s, int64_t need) {
+    const int64_t cap = 2 * need;
+    auto move = [&](auto *&ptr) {
+      using T = std::remove_reference_t<decltype(*ptr)>;
+      T *q = dev_alloc<T>((size_t)cap);
+      if (s.n) HIP_OK(hipMemcpy(q, ptr, (size_t)s.n * sizeof(T), hipMemcpyDeviceToDevice));
+      HIP_OK(hipFree(ptr));
+      ptr = q;
+    };
+    move(s.x); move(s.y); move(s.z); move(s.vx); move(s.vy); move(s.vz); move(s.t); move(s.w); move(s.e);
+    move(s.ip); move(s.jp); move(s.kp); move(s.blk); move(s.status); move(s.id); move(s.rng);
+    s.capacity = cap;
+  };
+  std::unique_ptr<jaybenne_amd::MeshData> md;
+  try {
+    md.reset(new jaybenne_amd::MeshData(pkg, v, prefix, grow));
+  } catch (const jaybenne_amd::Error &e) {
+    std::fprintf(stderr, "jb_mesh_create failed: %s\n", e.what());
+    MPI_Abort(MPI_COMM_WORLD, 4);
+  }
+  jb_mesh *mesh = md->mesh();
 
   // ---- the halo copies' material state: the owners' interior cells (the refresh a host repeats
   //      after every UpdateFluid when do_feedback is on; here once)
@@ -249,7 +284,7 @@ int main(int argc, char **argv) {
   }
 
   // ---- swarm: one pool per rank, room for every photon of the problem (they may all come here)
-  jb_swarm_view sw{};
+  jb_swarm_view &sw = md->swarm;
   sw.capacity = nparticles + nparticles / 4 + 4096;
   // (test knobs: a swarm with little room makes the runs close their holes on the way -- jb_exchange's
   // capacity protocol --, a tiny record buffer makes every rank stop together instead of one hanging the rest)
@@ -260,7 +295,6 @@ int main(int argc, char **argv) {
   sw.ip = dev_alloc<int32_t>(sw.capacity); sw.jp = dev_alloc<int32_t>(sw.capacity); sw.kp = dev_alloc<int32_t>(sw.capacity);
   sw.blk = dev_alloc<int32_t>(sw.capacity); sw.status = dev_alloc<int32_t>(sw.capacity);
   sw.id = dev_alloc<uint64_t>(sw.capacity); sw.rng = dev_alloc<uint64_t>(sw.capacity);
-  int32_t *prefix = dev_alloc<int32_t>((size_t)nb * nx);
 
   // ---- InitializeRadiation (jaybenne.cpp:570-578): thermal source block by block; stream ids
   //      are global creation indices, so every rank must know every block's count
@@ -276,6 +310,7 @@ int main(int argc, char **argv) {
   JB_OK(jb_source_photons_fill(ctx, mesh, &sw, JB_SOURCE_THERMAL, 0.0, 0.0, nper.data(), prefix,
                                plan.slot_base.data(), plan.id_base.data()));
   sw.n = plan.total_local;
+  md->next_id = plan.next_id;
 
   // total weight (host sum of this rank's photons), reduced over ranks
   auto total_weight = [&]() {
@@ -297,12 +332,12 @@ int main(int argc, char **argv) {
   int64_t *rec_dev = dev_alloc<int64_t>((size_t)sw.capacity / 4 * JB_RECORD_WORDS + JB_RECORD_WORDS);   // (allocated at full size)
   const int64_t rec_cap = std::getenv("JB_HANDOFF_REC_CAP") ? std::atoll(std::getenv("JB_HANDOFF_REC_CAP")) : sw.capacity / 4;
   // (jb_exchange: a receive buffer of its own -- both directions are in flight at once)
-  const bool one_call = std::strcmp(exchange, "tasks") != 0;
+  const bool one_call = std::strcmp(exchange, "tasks") != 0 && !one_step;
   int64_t *recv_dev = one_call ? dev_alloc<int64_t>((size_t)rec_cap * JB_RECORD_WORDS + JB_RECORD_WORDS) : nullptr;
   jb_exchange_transport tr{};
   MpiTransport mpi_tr{nranks};
   ncclComm_t nccl = nullptr;
-  if (std::strcmp(exchange, "mpi") == 0) {
+  if (std::strcmp(exchange, "mpi") == 0 || one_step) {
     tr.handle = &mpi_tr; tr.all_gather_u64 = mpi_all_gather_u64; tr.all_to_all_v = mpi_all_to_all_v;
   } else if (std::strcmp(exchange, "rccl") == 0) {
     ncclUniqueId uid;
@@ -334,6 +369,23 @@ int main(int argc, char **argv) {
   bool ok = true;
   double time = 0.0;
   for (int cyc = 0; cyc < cycles; ++cyc) {
+    if (one_step) {
+      // the whole cycle in one call: jb_radiation_step_ranks over the MPI transport
+      jaybenne_amd::TaskStatus ts = jaybenne_amd::TaskStatus::complete;
+      try {
+        ts = jaybenne_amd::RadiationStep(md.get(), time, p.dt, &tr, rank, nranks);
+      } catch (const jaybenne_amd::Error &e) {
+        std::fprintf(stderr, "RadiationStep failed (%d): %s\n", (int)e.status, e.what());
+        MPI_Abort(MPI_COMM_WORLD, 4);
+      }
+      if (ts != jaybenne_amd::TaskStatus::complete) {
+        std::fprintf(stderr, "RadiationStep did not finish in max_transport_iterations passes\n");
+        MPI_Abort(MPI_COMM_WORLD, 4);
+      }
+      iterations_total += md->last_step.transport_iterations;
+      handed_total += md->last_step.sent;
+      compactions_total += md->last_step.capacity_rounds;
+    } else {
     JB_OK(jb_update_derived_transport_fields(ctx, mesh, p.dt));
     JB_OK(jb_zero_energy_tally(ctx, mesh));
     int64_t first = 0;
@@ -392,6 +444,7 @@ int main(int argc, char **argv) {
       }
     }
     JB_OK(jb_remove_marked_particles(ctx, &sw));
+    }
     time += p.dt;
     // checks
     int64_t unfinished = 0;
@@ -421,7 +474,8 @@ int main(int argc, char **argv) {
   MPI_Allreduce(&ev, &ev_g, 1, MPI_LONG_LONG, MPI_SUM, MPI_COMM_WORLD);
   MPI_Allreduce(&handed_total, &handed_g, 1, MPI_LONG_LONG, MPI_SUM, MPI_COMM_WORLD);
   if (rank == 0 && compactions_total)
-    std::printf("jb_exchange reported JB_ERR_CAPACITY %lld time(s): holes closed, exchange repeated\n", compactions_total);
+    std::printf("jb_exchange reported JB_ERR_CAPACITY %lld time(s): %s, exchange repeated\n", compactions_total,
+                one_step ? "room made" : "holes closed");
   if (rank == 0)
     std::printf("%d rank(s), %d blocks, %d halo ring(s): %lld events, %lld photons handed between ranks in %lld "
                 "transport iterations (%.2f per cycle)  -> %s\n", nranks, nblocks_total, halo_rings, ev_g, handed_g,
@@ -458,8 +512,8 @@ int main(int argc, char **argv) {
   }
   const int rcode = ok && (nranks == 1 || handed_g > 0) ? 0 : 1;
   if (nccl) { jb_transport_release(&tr); ncclCommDestroy(nccl); }
-  jb_mesh_destroy(mesh);
-  jb_finalize(ctx);
+  md.reset();     // (the mesh, then the context: both before MPI goes away)
+  pkg.reset();
   MPI_Finalize();
   return rcode;
 }

@@ -462,6 +462,52 @@ double jb_estimate_timestep(const jb_context *ctx);
 jb_status jb_radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, double t_start,
                             double dt, uint64_t *next_id, uint32_t *cycle, int32_t *prefix_dev);
 
+/* RadiationStep(pmesh, t_start, dt) for a BLOCK-PARTITIONED mesh, on every rank -- jaybenne.cpp:68-151 with
+ * its iterate-sublist (:113-131) inside the call: derived fields; the emission source (blocks_in_call = the
+ * blocks this rank OWNS, sourcing.cpp:68-69; stream ids and slots by PlanSource of jaybenne_amd.hpp over every
+ * rank's counts; *next_id advances by the GLOBAL total); the census tally zeroed; then, at most
+ * max_transport_iterations times, transport of [first, n) with the fused census tally -> jb_exchange over
+ * comm->transport -> stop when nothing moved anywhere -> SampleDDMCBlockFace on the arrivals (DDMC); the
+ * marked particles removed; UpdateFluid.  The photons are those of the same task list driven by hand
+ * (jaybenne_amd/jaybenne.py) bit for bit.  DefragParticles (jb_defrag_policy) and the refresh of the halo
+ * copies after UpdateFluid stay with the host, as for jb_radiation_step.
+ *
+ * Collective contract: every rank of comm calls with the same cycle, t_start, dt and *next_id, and every
+ * rank returns the same status from the same call:
+ *   - the first collective is an all-gather of [status word | this rank's new photons per GLOBAL block],
+ *     made on every step (emission or not); before it the call checks its arguments, allocates all it
+ *     needs (the count matrix of jb_exchange, the record buffers, the gather buffer), counts the emission
+ *     and calls reserve for its new photons.  A rank that fails there puts its verdict in the status
+ *     word: every rank then returns that error (the lowest failing rank's), none is left in a collective;
+ *   - JB_ERR_CAPACITY of jb_exchange comes out on every rank in the same call: each grows the record
+ *     buffers the library owns (released by jb_release_scratch), closes its swarm's holes and calls
+ *     reserve if the swarm is still short, and all call again over [0, n) -- at most 4 calls per
+ *     transport iteration, then JB_ERR_CAPACITY on every rank (report->capacity_rounds counts them);
+ *   - JB_ITERATE when max_transport_iterations passes did not empty the sublist (moved_anywhere is global:
+ *     on every rank alike); neither tally nor fluid is then updated.
+ * The library's other failures (a HIP error in a kernel, a failing collective) are local, as in the
+ * task calls themselves.
+ * Checked first, with JB_ERR_INVALID and no collective: null pointers, rank outside [0, nranks) or not the
+ * mesh view's rank, nranks below the owners of the view, transport missing when nranks > 1, and a view
+ * with ONE owner under nranks > 1 -- a replicated mesh (every rank holds every block: jb_mesh_view cannot
+ * tell it from a single-rank mesh) is not driven by this call.  nranks == 1 with transport == NULL:
+ * exactly jb_radiation_step.  report may be NULL. */
+typedef struct jb_rank_comm {
+  int32_t rank, nranks;                     /* rank must equal the mesh view's rank */
+  const jb_exchange_transport *transport;   /* its two collectives; may be NULL when nranks == 1 */
+  void *host;                               /* handed back to reserve */
+  /* optional: room for >= n_slots particles (grow the device arrays, carry 0..n-1 over, update swarm's
+   * pointers and capacity); 0 = success.  NULL: the swarm must already have the room. */
+  int (*reserve)(void *host, jb_swarm_view *swarm, int64_t n_slots);
+} jb_rank_comm;
+typedef struct jb_step_report {
+  int32_t transport_iterations, capacity_rounds;
+  int64_t sent, received, events;           /* this rank, this step */
+} jb_step_report;
+jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, double t_start,
+                                  double dt, uint64_t *next_id, uint32_t *cycle, int32_t *prefix_dev,
+                                  const jb_rank_comm *comm, jb_step_report *report);
+
 /* ---- trace ranges -- the reference's Kokkos::Profiling::pushRegion("Jaybenne::Timestep") ...
  * popRegion() and "Jaybenne::TransportLoop" (jaybenne.cpp:87,115,127,145).  Every task entry point
  * above opens a ROCTx range named after its reference task ("Jaybenne::TransportPhotons_DDMC", ...)

@@ -9,8 +9,12 @@
 // for the reference.  examples/mcblock_amd.cpp is a complete host application written on it;
 // jaybenne_amd/jaybenne.py is the same mirror in Python (and adds the multi-rank hand-off).
 //
-// Single rank only: RadiationStep here is the task list of jaybenne.cpp:104-138 for a mesh held
-// by one rank, where one transport launch resolves every block crossing in flight.
+// RadiationStep comes in two overloads: RadiationStep(md, t_start, dt) is the task list of
+// jaybenne.cpp:104-138 for a mesh held by one rank, where one transport launch resolves every block
+// crossing in flight; RadiationStep(md, t_start, dt, transport, rank, nranks) runs it on every rank of a
+// block-partitioned mesh, the iterate-sublist (transport, hand-off, completion test) inside one library
+// call (jb_radiation_step_ranks) over the host's jb_exchange_transport (MPI, RCCL, ...).  Halo refresh
+// and replicated meshes stay with the host (examples/handoff_mpi.cpp, jaybenne_amd/jaybenne.py).
 #ifndef JAYBENNE_AMD_HPP_
 #define JAYBENNE_AMD_HPP_
 
@@ -103,6 +107,16 @@ class MeshData {
     if (n > swarm.capacity) throw Error(JB_ERR_CAPACITY, "swarm pool could not be grown");
   }
 
+  // jb_rank_comm::reserve of the multi-rank RadiationStep: the host's pool growth, 0 = success
+  static int ReserveTrampoline(void *host, jb_swarm_view *swarm, int64_t n) {
+    try {
+      static_cast<MeshData *>(host)->reserve_(*swarm, n);
+    } catch (...) {
+      return 1;
+    }
+    return swarm->capacity >= n ? 0 : 1;
+  }
+
   jb_swarm_view swarm{};   // n, capacity and the device arrays
   uint64_t next_id = 0;    // first unused random-stream id
   uint64_t cycle = 0;      // RadiationStep counter (keys the per-cell rounding streams: SourceEpoch); 0 = initialisation
@@ -113,6 +127,7 @@ class MeshData {
   int defrag_interval = -1;
   int defrags = 0;
   int steps_since_defrag = 0;
+  jb_step_report last_step{};   // what the last multi-rank RadiationStep did on this rank
 
  private:
   std::shared_ptr<StateDescriptor> pkg_;
@@ -517,6 +532,20 @@ struct TraceRange {
   TraceRange &operator=(const TraceRange &) = delete;
 };
 
+// (not in the reference's task list: DefragParticles at the end of a cycle, on the library's schedule or every
+// k-th cycle)
+inline void DefragAfterStep(MeshData *md, int64_t events) {
+  if (md->defrag_interval < 0) {
+    int32_t sorted = 0;
+    Check(jb_defrag_policy(md->ctx(), md->mesh(), &md->swarm, events, JB_DEFRAG_DECIDE_AND_SORT, &sorted));
+    md->defrags += sorted;
+  } else if (md->defrag_interval > 0 && ++md->steps_since_defrag >= md->defrag_interval) {
+    DefragParticles(md);
+    md->steps_since_defrag = 0;
+    ++md->defrags;
+  }
+}
+
 // jaybenne::RadiationStep(pmesh, t_start, dt) for one rank -- jaybenne.cpp:68-151
 inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt) {
   TraceRange timestep("Jaybenne::Timestep");
@@ -540,17 +569,34 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt)
   md->events += after.n_events - before.n_events;
   if (CheckCompletion(md, t_start + dt) != TaskStatus::complete) return TaskStatus::iterate;
   UpdateFluid(md);
-  // (not in the reference's task list: DefragParticles on the library's schedule, or every k-th cycle)
-  if (md->defrag_interval < 0) {
-    int32_t sorted = 0;
-    Check(jb_defrag_policy(md->ctx(), md->mesh(), &md->swarm, after.n_events - before.n_events,
-                           JB_DEFRAG_DECIDE_AND_SORT, &sorted));
-    md->defrags += sorted;
-  } else if (md->defrag_interval > 0 && ++md->steps_since_defrag >= md->defrag_interval) {
-    DefragParticles(md);
-    md->steps_since_defrag = 0;
-    ++md->defrags;
-  }
+  DefragAfterStep(md, after.n_events - before.n_events);
+  return TaskStatus::complete;
+}
+
+// jaybenne::RadiationStep(pmesh, t_start, dt) on every rank of a block-partitioned mesh -- jaybenne.cpp:68-151
+// with the iterate-sublist of :113-131 inside ONE library call, jb_radiation_step_ranks (collective: every rank
+// calls it in the same cycle; see its contract in jaybenne_amd.h).  tr: the two collectives of the hand-off
+// (may be NULL with nranks == 1); the swarm grows through MeshData's reserve.  JB_ITERATE (max_transport_iterations
+// passes did not finish the sublist) comes back as TaskStatus::iterate on every rank; errors throw on every rank.
+// The refresh of the halo copies after UpdateFluid stays with the host.  DefragParticles: as the single-rank
+// overload, each rank on its own (a host whose ranks should sort together reduces JB_DEFRAG_DECIDE itself).
+inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt, const jb_exchange_transport *tr,
+                                int rank, int nranks) {
+  jb_rank_comm comm{};
+  comm.rank = rank;
+  comm.nranks = nranks;
+  comm.transport = tr;
+  comm.host = md;
+  comm.reserve = &MeshData::ReserveTrampoline;
+  uint32_t cycle = (uint32_t)md->cycle;
+  jb_step_report rep{};
+  const jb_status st = jb_radiation_step_ranks(md->ctx(), md->mesh(), &md->swarm, t_start, dt, &md->next_id, &cycle,
+                                               md->prefix_dev(), &comm, &rep);
+  md->cycle = cycle;
+  md->last_step = rep;
+  if (Check(st) != TaskStatus::complete) return TaskStatus::iterate;
+  md->events += rep.events;
+  DefragAfterStep(md, rep.events);
   return TaskStatus::complete;
 }
 

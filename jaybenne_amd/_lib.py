@@ -102,6 +102,20 @@ class ExchangeTransport(C.Structure):
     _fields_ = [("handle", C.c_void_p), ("all_gather_u64", ALL_GATHER_FN), ("all_to_all_v", ALL_TO_ALL_V_FN)]
 
 
+# jb_rank_comm / jb_step_report of jb_radiation_step_ranks (include/jaybenne_amd.h)
+RESERVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(SwarmView), C.c_int64)
+
+
+class RankComm(C.Structure):
+    _fields_ = [("rank", C.c_int32), ("nranks", C.c_int32), ("transport", C.POINTER(ExchangeTransport)),
+                ("host", C.c_void_p), ("reserve", RESERVE_FN)]
+
+
+class StepReport(C.Structure):
+    _fields_ = [("transport_iterations", C.c_int32), ("capacity_rounds", C.c_int32),
+                ("sent", C.c_int64), ("received", C.c_int64), ("events", C.c_int64)]
+
+
 # every entry point include/jaybenne_amd.h declares: name -> (restype, argtypes)
 _vp, _i64, _f64, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
 PROTOTYPES = {
@@ -149,6 +163,8 @@ PROTOTYPES = {
     "jb_estimate_timestep": (_f64, [_vp]),
     "jb_radiation_step": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64,
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _vp]),
+    "jb_radiation_step_ranks": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint32), _vp, C.POINTER(RankComm), C.POINTER(StepReport)]),
     "jb_range_push": (_int, [C.c_char_p]),
     "jb_range_pop": (_int, []),
     "jb_ranges_enabled": (_int, []),

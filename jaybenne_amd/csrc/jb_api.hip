@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/jaybenne_amd.h"
+#include "../../include/jaybenne_amd.hpp"   // PlanSource: the stream-id arithmetic every host shares
 #include "jb_kernels.hpp"
 #include "jb_kernel_hybrid.hpp"
 #include "jb_kernel_ddmc_q.hpp"
@@ -62,6 +63,13 @@ struct jb_context {
   std::vector<long long> xch_tab;             // ... this rank's send / receive counts and offsets
   unsigned long long xch_room[3] = {0, 0, 0}; // ... and its room: send buffer, receive buffer, free swarm slots (records)
   size_t scratch_words = 0;
+  // jb_radiation_step_ranks: the hand-off record buffers (JB_RECORD_WORDS words per record) and the buffer of
+  // the step's first all-gather ([status | counts per global block] of this rank, then every rank's)
+  long long *step_send_d = nullptr, *step_recv_d = nullptr;
+  long long step_send_cap = 0, step_recv_cap = 0;
+  unsigned long long *step_gather_d = nullptr;
+  size_t step_gather_words = 0;
+  long long min_records = 0;  // JB_HANDOFF_MIN_RECORDS at jb_initialize: first size of those record buffers (tests)
   // arithmetic of the gray IMC tracking step: lean (default) or exact (JB_EXACT_ARITH=1 in the
   // environment at jb_initialize, or jb_set_arithmetic)
   bool lean_arith = true;
@@ -121,6 +129,11 @@ struct jb_mesh {
   // one synchronisation; the further transport iterations of a multi-rank cycle reuse the answer)
   int not_all_ddmc_host = -1;
   int nclass_host = 0;   // ... and the number of distinct step records (DevMesh::ddmc_code), read with it
+  // host copies of the view for jb_radiation_step_ranks: global id of each resident block, blocks owned
+  // here, and whether every block of the view has the same owner (a single-rank or replicated view)
+  std::vector<int32_t> gid_host;
+  int nowned = 0;
+  bool one_owner = true;
 };
 
 __global__ void k_rcp_refined(double b, double *out) { *out = m_rcp_refined(b); }
@@ -246,6 +259,7 @@ extern "C" jb_status jb_initialize(const jb_params *params, const jb_eos *eos,
   if (const char *e = getenv("JB_COOP_GATHER")) ctx->coop_gather = e[0] == '1' ? 1 : (e[0] == '2' ? 2 : (e[0] == '4' ? 4 : 0));  // (tests, A/B runs)
   if (const char *e = getenv("JB_DDMC_QUEUES")) ctx->ddmc_queues = e[0] != '0';
   if (const char *e = getenv("JB_DDMC_LDS_CODES")) ctx->ddmc_lds_codes = e[0] != '0';
+  if (const char *e = getenv("JB_HANDOFF_MIN_RECORDS")) ctx->min_records = atoll(e) > 0 ? atoll(e) : 0;
   if (const char *e = getenv("JB_DDMC_MAX_CLASSES")) {   // (tests: the fall-back when a mesh has more distinct step records)
     const int v = atoi(e);
     ctx->max_classes = v < 0 ? 0 : (v > kMaxClasses ? kMaxClasses : v);
@@ -321,6 +335,9 @@ extern "C" jb_status jb_finalize(jb_context *ctx) {
   if (ctx->counters_h) (void)hipHostFree(ctx->counters_h);
   if (ctx->scratch_d) (void)hipFree(ctx->scratch_d);
   if (ctx->xch_d) (void)hipFree(ctx->xch_d);
+  if (ctx->step_send_d) (void)hipFree(ctx->step_send_d);
+  if (ctx->step_recv_d) (void)hipFree(ctx->step_recv_d);
+  if (ctx->step_gather_d) (void)hipFree(ctx->step_gather_d);
   for (hipEvent_t e : ctx->tev) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->sort_ev) if (e) (void)hipEventDestroy(e);
   delete ctx;
@@ -451,6 +468,9 @@ extern "C" jb_status jb_mesh_create(jb_context *ctx, const jb_mesh_view *v, jb_m
   int maxrank = 0;
   for (int g = 0; g < v->nblocks_total; ++g) maxrank = v->owner[g] > maxrank ? v->owner[g] : maxrank;
   m->nranks_seen = maxrank + 1;
+  m->gid_host.assign(v->gid, v->gid + v->nblocks);
+  for (int b = 0; b < v->nblocks; ++b) m->nowned += (!v->owned || v->owned[b]) ? 1 : 0;
+  for (int g = 1; g < v->nblocks_total; ++g) m->one_owner = m->one_owner && v->owner[g] == v->owner[0];
   jb_status st;
 #define UP(field, count)                                                         \
   if ((st = upload(m, v->field, (size_t)(count), &D.field)) != JB_COMPLETE) {     \
@@ -1443,6 +1463,13 @@ extern "C" jb_status jb_release_scratch(jb_context *ctx) {
   if (ctx->scratch_d) JB_HIP(hipFree(ctx->scratch_d));
   ctx->scratch_d = nullptr;
   ctx->scratch_words = 0;
+  if (ctx->step_send_d) JB_HIP(hipFree(ctx->step_send_d));
+  if (ctx->step_recv_d) JB_HIP(hipFree(ctx->step_recv_d));
+  if (ctx->step_gather_d) JB_HIP(hipFree(ctx->step_gather_d));
+  ctx->step_send_d = ctx->step_recv_d = nullptr;
+  ctx->step_send_cap = ctx->step_recv_cap = 0;
+  ctx->step_gather_d = nullptr;
+  ctx->step_gather_words = 0;
   return JB_COMPLETE;
 }
 
@@ -1627,6 +1654,23 @@ extern "C" jb_status jb_unpack_incoming(jb_context *ctx, jb_mesh *mesh, jb_swarm
   return JB_COMPLETE;
 }
 
+// the rank x rank count matrix of jb_exchange (+ its pack offsets), in a buffer of the context's own
+static jb_status ensure_count_matrix(jb_context *ctx, int nranks) {
+  if (!ctx->xch_d || ctx->xch_ranks < nranks) {
+    if (ctx->xch_d) (void)hipFree(ctx->xch_d);
+    const size_t R = nranks > 64 ? (size_t)nranks : 64;
+    if (hipMalloc(&ctx->xch_d, R * (R + 8) * sizeof(unsigned long long)) == hipSuccess) {
+      ctx->xch_ranks = (int)R;
+    } else {
+      ctx->xch_d = nullptr;
+      ctx->xch_ranks = 0;
+      (void)hipGetLastError();
+      return fail(JB_ERR_HIP, "jb_exchange: hipMalloc of the count matrix failed");
+    }
+  }
+  return JB_COMPLETE;
+}
+
 // ------------------------------------------------------------------------------------------------
 // jb_exchange: MeshResetCommunication -> MeshSend -> MeshReceive (jaybenne.cpp:26-61) as ONE call on the
 // context's stream, the records never leaving the device.  What moves the bytes is a jb_exchange_transport
@@ -1669,18 +1713,8 @@ extern "C" jb_status jb_exchange(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *
   // (the count matrix lives in a buffer of its own, taken on the FIRST call of a context -- before any rank has
   // entered a collective of the run's hot loop; a rank that cannot get its few KB fails there, and says so
   // in the gathered row of every later call: a rank-local failure must not leave the others in a collective)
-  if (!ctx->xch_d || ctx->xch_ranks < nranks) {
-    if (ctx->xch_d) (void)hipFree(ctx->xch_d);
-    const size_t R = nranks > 64 ? (size_t)nranks : 64;
-    if (hipMalloc(&ctx->xch_d, R * (R + 8) * sizeof(unsigned long long)) == hipSuccess) {
-      ctx->xch_ranks = (int)R;
-    } else {
-      ctx->xch_d = nullptr;
-      ctx->xch_ranks = 0;
-      (void)hipGetLastError();
-      return fail(JB_ERR_HIP, "jb_exchange: hipMalloc of the count matrix failed");
-    }
-  }
+  st = ensure_count_matrix(ctx, nranks);
+  if (st != JB_COMPLETE) return st;
   unsigned long long *matrix_d = ctx->xch_d;
   if (tr->all_gather_u64(tr->handle, (const uint64_t *)per_rank, (uint64_t *)matrix_d, row, (void *)ctx->stream) != 0)
     return fail(JB_ERR_HIP, "jb_exchange: the transport's all-gather of the record counts failed");
@@ -1929,6 +1963,203 @@ extern "C" jb_status jb_radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_
     if (st != JB_COMPLETE) return st;
   }
   return jb_update_fluid(ctx, mesh);
+}
+
+// ------------------------------------------------------------------------------------------------
+// RadiationStep across ranks: the task list of jaybenne.cpp:104-138 with the iterate-sublist of :113-131
+// (transport -> MeshSend / MeshReceive -> SampleDDMCBlockFace -> global completion test) inside the call,
+// step for step what jaybenne_amd/jaybenne.py drives through the task entry points.
+
+// a hand-off record buffer of the library's own, grown to at least `records` (its contents are not kept)
+static jb_status ensure_records(long long **buf, long long *cap, long long records) {
+  if (*buf && *cap >= records) return JB_COMPLETE;
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr;
+  *cap = 0;
+  if (hipMalloc(buf, (size_t)records * kRecWords * sizeof(long long)) != hipSuccess) {
+    *buf = nullptr;
+    (void)hipGetLastError();
+    return fail(JB_ERR_HIP, "hipMalloc of a hand-off buffer of %lld records failed", records);
+  }
+  *cap = records;
+  return JB_COMPLETE;
+}
+
+// room for n_slots particles: the host's reserve, if it gave one
+static jb_status step_reserve(const jb_rank_comm *comm, jb_swarm_view *swarm, int64_t n_slots) {
+  if (n_slots <= swarm->capacity) return JB_COMPLETE;
+  if (comm->reserve && comm->reserve(comm->host, swarm, n_slots) == 0 && swarm->capacity >= n_slots)
+    return check_swarm(swarm, "jb_radiation_step_ranks (after reserve)");
+  return fail(JB_ERR_CAPACITY, "swarm capacity %lld too small for %lld particles%s", (long long)swarm->capacity,
+              (long long)n_slots, comm->reserve ? " (reserve did not make the room)" : "");
+}
+
+extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm,
+                                             double t_start, double dt, uint64_t *next_id, uint32_t *cycle,
+                                             int32_t *prefix_dev, const jb_rank_comm *comm,
+                                             jb_step_report *report) {
+  // what is the same on every rank (or makes a collective impossible): checked before any of them
+  if (!comm) return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: null comm");
+  const int rank = comm->rank, nranks = comm->nranks;
+  if (nranks < 1 || rank < 0 || rank >= nranks)
+    return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: rank %d outside [0, nranks = %d)", rank, nranks);
+  const jb_exchange_transport *tr = comm->transport;
+  if (nranks > 1 && (!tr || !tr->all_gather_u64 || !tr->all_to_all_v))
+    return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: %d ranks need a transport with both collectives", nranks);
+  if (!ctx || !mesh || !swarm || !next_id || !cycle)
+    return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: null argument");
+  const DevMesh &M = mesh->dm;
+  if (nranks > 1 && mesh->one_owner)
+    return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: every block of the mesh view has the same owner -- a "
+                "replicated (or single-rank) mesh, which this call does not drive across %d ranks", nranks);
+  if (nranks < mesh->nranks_seen || nranks + 3 > kRankEnd - kRankBase)
+    return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: nranks = %d does not cover the owners in the mesh view", nranks);
+  JB_HIP(hipSetDevice(ctx->device));
+  const bool multi = nranks > 1;
+  const bool ddmc = ctx->params.use_ddmc != 0;
+  jb_step_report rep{};
+  auto done = [&](jb_status st) {
+    if (report) *report = rep;
+    return st;
+  };
+  JB_RANGE("Jaybenne::Timestep");               // jaybenne.cpp:87 ... :145
+  const uint32_t epoch = *cycle + 1;             // (*cycle advances once every rank got this far)
+  const size_t row = 1 + (size_t)M.nblocks_total;   // what a rank puts into the first all-gather
+  std::vector<int32_t> nper(M.nblocks, 0);
+  // this rank's part up to the first collective: a failure goes into the gathered status word
+  auto local_part = [&]() -> jb_status {
+    // the gather buffer first (without it this rank could not say anything: the one failure it cannot
+    // share), then the rest of what the step allocates
+    const size_t words = row * (size_t)(nranks + 1);
+    if (multi && ctx->step_gather_words < words) {
+      if (ctx->step_gather_d) (void)hipFree(ctx->step_gather_d);
+      ctx->step_gather_words = 0;
+      if (hipMalloc(&ctx->step_gather_d, words * sizeof(unsigned long long)) != hipSuccess) {
+        ctx->step_gather_d = nullptr;
+        (void)hipGetLastError();
+        return fail(JB_ERR_HIP, "jb_radiation_step_ranks: hipMalloc of the gather buffer failed");
+      }
+      ctx->step_gather_words = words;
+    }
+    jb_status st = check_swarm(swarm, "jb_radiation_step_ranks");
+    if (st != JB_COMPLETE) return st;
+    if (M.rank != rank)
+      return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: comm rank %d is not the mesh view's rank %d", rank, M.rank);
+    if (*cycle >= (1u << 19) - 1u)   // (SourceEpoch, as jb_radiation_step)
+      return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: cycle counter %u at the limit of the source epochs (2^19 - 1)", *cycle);
+    if (ctx->params.do_emission && !prefix_dev)
+      return fail(JB_ERR_INVALID, "emission source needs the prefix workspace");
+    if (multi) {
+      if ((st = ensure_count_matrix(ctx, nranks)) != JB_COMPLETE) return st;
+      if (!ctx->step_send_d || !ctx->step_recv_d) {
+        // (JB_HANDOFF_MIN_RECORDS: a small first size, so that the tests walk through the capacity protocol)
+        const long long start = ctx->min_records > 0 ? ctx->min_records : (swarm->n / 16 > 4096 ? swarm->n / 16 : 4096);
+        if ((st = ensure_records(&ctx->step_send_d, &ctx->step_send_cap, start)) != JB_COMPLETE) return st;
+        if ((st = ensure_records(&ctx->step_recv_d, &ctx->step_recv_cap, start)) != JB_COMPLETE) return st;
+      }
+    }
+    if ((st = jb_update_derived_transport_fields(ctx, mesh, dt)) != JB_COMPLETE) return st;
+    if (ctx->params.do_emission) {
+      // SourcePhotons (md.nowned blocks in the call, sourcing.cpp:68-69); halo copies source nothing
+      st = jb_source_photons_count(ctx, mesh, JB_SOURCE_EMISSION, dt, mesh->nowned, epoch, nper.data(), prefix_dev);
+      if (st != JB_COMPLETE) return st;
+      int64_t tot = 0;
+      for (int b = 0; b < M.nblocks; ++b) tot += nper[b];
+      if ((st = step_reserve(comm, swarm, swarm->n + tot)) != JB_COMPLETE) return st;
+    }
+    return JB_COMPLETE;
+  };
+  const jb_status local = local_part();
+  if (multi && !ctx->step_gather_d) return done(local);
+  // the first collective: [status | new photons per global block] of every rank
+  std::vector<unsigned long long> mine(row, 0), all(row * (size_t)nranks, 0);
+  if (local != JB_COMPLETE) {
+    mine[0] = (unsigned long long)(-(long long)local);
+  } else {
+    for (int b = 0; b < M.nblocks; ++b) mine[1 + (size_t)mesh->gid_host[b]] = (unsigned long long)nper[b];
+  }
+  if (multi) {
+    unsigned long long *in_d = ctx->step_gather_d, *all_d = ctx->step_gather_d + row;
+    JB_HIP(hipMemcpyAsync(in_d, mine.data(), row * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+    if (tr->all_gather_u64(tr->handle, (const uint64_t *)in_d, (uint64_t *)all_d, (int)row, (void *)ctx->stream) != 0)
+      return done(fail(JB_ERR_HIP, "jb_radiation_step_ranks: the transport's all-gather of the source counts failed"));
+    JB_HIP(hipMemcpyAsync(all.data(), all_d, all.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    JB_HIP(hipStreamSynchronize(ctx->stream));
+  } else {
+    all = mine;
+  }
+  for (int q = 0; q < nranks; ++q) {
+    const unsigned long long w = all[(size_t)q * row];
+    if (w == 0) continue;
+    if (q == rank) return done(local);          // (jb_last_error: this rank's own reason)
+    return done(fail((jb_status)(-(long long)w), "jb_radiation_step_ranks: rank %d failed before the step's first "
+                     "collective (status %d)", q, -(int)(long long)w));
+  }
+  *cycle = epoch;   // (keys the per-cell rounding streams of this cycle's emission source: SourceEpoch)
+  jb_status st = JB_COMPLETE;
+  if (ctx->params.do_emission) {
+    std::vector<long long> all_counts((size_t)M.nblocks_total, 0);
+    for (int q = 0; q < nranks; ++q)
+      for (size_t g = 0; g < (size_t)M.nblocks_total; ++g) all_counts[g] += (long long)all[(size_t)q * row + 1 + g];
+    const jaybenne_amd::SourcePlan pl = jaybenne_amd::PlanSource(nper, mesh->gid_host, all_counts, *next_id, swarm->n);
+    st = jb_source_photons_fill(ctx, mesh, swarm, JB_SOURCE_EMISSION, t_start, dt, nper.data(), prefix_dev,
+                                pl.slot_base.data(), pl.id_base.data());
+    if (st != JB_COMPLETE) return done(st);
+    swarm->n += pl.total_local;
+    *next_id = pl.next_id;
+  }
+  if ((st = jb_zero_energy_tally(ctx, mesh)) != JB_COMPLETE) return done(st);
+  jb_transport_stats before;
+  if ((st = jb_get_transport_stats(ctx, &before, 0)) != JB_COMPLETE) return done(st);
+  bool finished = false;
+  {
+    JB_RANGE("Jaybenne::TransportLoop");        // jaybenne.cpp:115 ... :127
+    constexpr int kExchangeCalls = 4;           // jb_exchange calls per transport iteration (capacity protocol)
+    int64_t first = 0;
+    for (int it = 0; it < ctx->params.max_transport_iterations; ++it) {
+      const int64_t last = swarm->n;
+      st = (ddmc ? jb_transport_photons_ddmc : jb_transport_photons)(ctx, mesh, swarm, t_start, dt, first, last, 1);
+      if (st != JB_COMPLETE) return done(st);
+      ++rep.transport_iterations;
+      if (!multi) { finished = true; break; }   // (every block crossing was resolved in flight)
+      int64_t nsent = 0, nrecv = 0, moved = 0, xf = first, xl = last;
+      for (int call = 1;; ++call) {
+        st = jb_exchange(ctx, mesh, swarm, xf, xl, rank, nranks, tr, (int64_t *)ctx->step_send_d, ctx->step_send_cap,
+                         (int64_t *)ctx->step_recv_d, ctx->step_recv_cap, &nsent, &nrecv, &moved);
+        if (st != JB_ERR_CAPACITY || call == kExchangeCalls) break;
+        // The verdict is the same on every rank: each makes the room IT lacks and all call again.  A failure
+        // to grow leaves the room short, and the next verdict -- again the same everywhere -- says so.
+        ++rep.capacity_rounds;
+        if (nsent > ctx->step_send_cap) (void)ensure_records(&ctx->step_send_d, &ctx->step_send_cap, nsent * 3 / 2 + 16);
+        if (nrecv > ctx->step_recv_cap) (void)ensure_records(&ctx->step_recv_d, &ctx->step_recv_cap, nrecv * 3 / 2 + 16);
+        if (swarm->n + nrecv > swarm->capacity) {
+          // close the holes earlier departures left; what still has to go is found by its status
+          if ((st = jb_remove_marked_particles(ctx, swarm)) != JB_COMPLETE) return done(st);
+          (void)step_reserve(comm, swarm, swarm->n + nrecv);
+          xf = 0;
+          xl = swarm->n;
+        }
+      }
+      if (st != JB_COMPLETE) return done(st);
+      rep.sent += nsent;
+      rep.received += nrecv;
+      if (moved == 0) { finished = true; break; }   // CheckCompletion with its global sync (jaybenne.cpp:130-131)
+      first = swarm->n - nrecv;                     // the arrivals, appended at the end of the swarm
+      if (ddmc && nrecv > 0 && (st = jb_sample_ddmc_block_face(ctx, mesh, swarm, first, swarm->n)) != JB_COMPLETE)
+        return done(st);
+    }
+  }
+  if (!finished) return done(JB_ITERATE);
+  jb_transport_stats after;
+  if ((st = jb_get_transport_stats(ctx, &after, 0)) != JB_COMPLETE) return done(st);
+  rep.events = after.n_events - before.n_events;
+  if (!multi && after.n_outgoing != before.n_outgoing)
+    return done(fail(JB_ERR_INVALID, "particles left for another rank in a single-rank step"));
+  if (after.n_absorbed != before.n_absorbed || after.n_escaped != before.n_escaped ||
+      after.n_outgoing != before.n_outgoing) {
+    if ((st = jb_remove_marked_particles(ctx, swarm)) != JB_COMPLETE) return done(st);
+  }
+  return done(jb_update_fluid(ctx, mesh));
 }
 
 // ------------------------------------------------------------------------------------------------

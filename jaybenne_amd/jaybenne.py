@@ -234,11 +234,15 @@ class MeshData:
         # How particles are handed to other ranks: "c" (default) = the library's jb_exchange in one call, over a
         # communicator of its own on an RCCL process group and over torch.distributed callbacks otherwise
         # ("c-rccl" / "c-torch" force one); "python" = the same protocol driven from here (comm.py: count
-        # kernel, read-back, all-gather, all-to-all-v from Python), kept for A/B.  JB_HANDOFF overrides.
+        # kernel, read-back, all-gather, all-to-all-v from Python), kept for A/B; "step" = the whole cycle, its
+        # iterate-sublist included, as ONE library call (jb_radiation_step_ranks) whose hand-off is jb_exchange over
+        # the transport "c" picks (a replicated mesh keeps its own path).  JB_HANDOFF overrides.
         self.handoff = os.environ.get("JB_HANDOFF", "c")
-        if self.handoff not in ("c", "c-torch", "c-rccl", "python"):
-            raise ValueError(f"JB_HANDOFF = {self.handoff!r}: one of c, c-torch, c-rccl, python")
+        if self.handoff not in ("c", "c-torch", "c-rccl", "python", "step"):
+            raise ValueError(f"JB_HANDOFF = {self.handoff!r}: one of c, c-torch, c-rccl, python, step")
         self._chandoff = None
+        self._rank_comm = None      # JB_HANDOFF=step: the jb_rank_comm of the library call (and its reserve callback)
+        self.step_report = None     # ... and the jb_step_report of the last cycle
         # DefragParticles after every k-th RadiationStep (0: never; the reference schedules none)
         # DefragParticles: -1 (default) on the library's schedule (jb_defrag_policy: when a cycle costs
         # 10 % more per event than the best one since the last sort), k > 0 after every k-th cycle,
@@ -323,12 +327,16 @@ class MeshData:
         inside the first exchange."""
         if self.handoff != "python" and self._chandoff is None and self.comm is not None:
             from .handoff import CHandoff
-            self._chandoff = CHandoff.make(self, {"c": "auto", "c-torch": "torch", "c-rccl": "rccl"}[self.handoff])
+            self._chandoff = CHandoff.make(self, {"c": "auto", "c-torch": "torch", "c-rccl": "rccl",
+                                                  "step": "auto"}[self.handoff])
 
     def handoff_path(self) -> str:
         """What the hand-off of this MeshData runs through (bench.py: ``handoff.path``)."""
         if self.handoff == "python":
             return "python: comm.py (count kernel, read-back, all-gather and all-to-all-v driven from Python)"
+        if self.handoff == "step" and not self.replicated:
+            inner = f"hand-off {self._chandoff.path}" if self._chandoff is not None else "one rank, no hand-off"
+            return f"c: jb_radiation_step_ranks (one call per cycle; {inner})"
         return self._chandoff.path if self._chandoff is not None else "c: jb_exchange (no exchange has run yet)"
 
     def close(self) -> None:
@@ -652,8 +660,58 @@ def RadiationStep(md: MeshData, t_start: float, dt: float) -> TaskStatus:
     for another rank's blocks, SampleDDMCBlockFace on the arrivals, and the global completion
     test (one all-reduced integer) -- repeated until no particle is in flight anywhere.
     """
+    if md.handoff == "step" and not md.replicated:
+        return _radiation_step_ranks(md, t_start, dt)   # (the library opens the reference's trace ranges itself)
     with _Range(md, "Jaybenne::Timestep"):          # jaybenne.cpp:87 ... :145
         return _radiation_step(md, t_start, dt)
+
+
+def _radiation_step_ranks(md: MeshData, t_start: float, dt: float) -> TaskStatus:
+    """JB_HANDOFF=step: the cycle of ``_radiation_step`` + ``_transport_loop`` as one library call,
+    ``jb_radiation_step_ranks`` (include/jaybenne_amd.h) -- the same photons.  The hand-off runs through the
+    transport of ``CHandoff.make(md, "auto")``; the swarm grows through ``md.reserve``."""
+    pkg = md.pkg
+    if md._rank_comm is None:
+        transport = None
+        if md.nranks > 1:
+            md.ensure_handoff()
+            transport = C.pointer(md._chandoff.tr)
+
+        def reserve(_host, _swarm, n_slots):
+            # (the library passes md.sv itself, which md.reserve updates in place)
+            try:
+                md.reserve(int(n_slots))
+                return 0
+            except Exception as e:   # noqa: BLE001 -- nothing may propagate through the C frames
+                md._reserve_error = e
+                return 1
+
+        cb = _lib.RESERVE_FN(reserve)
+        md._rank_comm = (_lib.RankComm(rank=md.rank, nranks=md.nranks, transport=transport, host=None, reserve=cb), cb)
+    md._reserve_error = None
+    md._sync_stream()
+    next_id, cycle, rep = C.c_uint64(md.next_id), C.c_uint32(md.cycle), _lib.StepReport()
+    st = md.lib.jb_radiation_step_ranks(pkg.ctx, md.handle, C.byref(md.sv), t_start, dt, C.byref(next_id),
+                                        C.byref(cycle), md.prefix.data_ptr(), C.byref(md._rank_comm[0]),
+                                        C.byref(rep))
+    md.next_id, md.cycle = int(next_id.value), int(cycle.value)
+    md._stats_cache = None       # (the counters moved inside the call)
+    md.step_report = rep
+    md.transport_iterations = int(rep.transport_iterations)
+    md.transport_iterations_total += int(rep.transport_iterations)
+    md.handoff_records += int(rep.sent)
+    if st < 0:
+        err = getattr(md._chandoff, "error", None) if md._chandoff is not None else None
+        if err is not None:
+            raise RuntimeError(f"hand-off transport failed: {err!r}")
+        if md._reserve_error is not None and st == _lib.JB_ERR_CAPACITY:
+            raise MemoryError(f"{md.lib.jb_last_error().decode()} ({md._reserve_error})")
+        _lib.check(st)
+    if st == _lib.JB_ITERATE:
+        return TaskStatus.iterate
+    md.events += int(rep.events)
+    _defrag_after_step(md, int(rep.events))
+    return TaskStatus.complete
 
 
 def _transport_loop(md: MeshData, transport, use_ddmc: bool, t_start: float, dt: float) -> bool:
@@ -727,23 +785,28 @@ def _radiation_step(md: MeshData, t_start: float, dt: float) -> TaskStatus:
             RemoveMarkedParticles(md)
         md.events += after["n_events"] - before["n_events"]
         UpdateFluid(md)
-        md._steps_since_defrag += 1
-        if md.defrag_interval < 0:
-            sorted_ = C.c_int32(0)
-            events = int(after["n_events"] - before["n_events"])
-            if md.nranks == 1:
-                _lib.check(md.lib.jb_defrag_policy(pkg.ctx, md.handle, C.byref(md.sv), events, 0, C.byref(sorted_)))
-            else:
-                # the ranks sort together: a cycle is as long as its slowest rank (jaybenne_amd.h)
-                _lib.check(md.lib.jb_defrag_policy(pkg.ctx, md.handle, C.byref(md.sv), events, 1, C.byref(sorted_)))
-                if md.comm.allreduce_max_float(float(sorted_.value)) > 0.0:
-                    _lib.check(md.lib.jb_defrag_policy(pkg.ctx, md.handle, C.byref(md.sv), events, 2, C.byref(sorted_)))
-                else:
-                    sorted_.value = 0
-            if sorted_.value:
-                md.defrags += 1
-                md._steps_since_defrag = 0
-        elif md.defrag_interval > 0 and md._steps_since_defrag >= md.defrag_interval:
-            DefragParticles(md)
-            md._steps_since_defrag = 0
+        _defrag_after_step(md, int(after["n_events"] - before["n_events"]))
     return TaskStatus.complete
+
+
+def _defrag_after_step(md: MeshData, events: int) -> None:
+    """DefragParticles at the end of a cycle: on the library's schedule (jb_defrag_policy) or every k-th cycle."""
+    pkg = md.pkg
+    md._steps_since_defrag += 1
+    if md.defrag_interval < 0:
+        sorted_ = C.c_int32(0)
+        if md.nranks == 1:
+            _lib.check(md.lib.jb_defrag_policy(pkg.ctx, md.handle, C.byref(md.sv), events, 0, C.byref(sorted_)))
+        else:
+            # the ranks sort together: a cycle is as long as its slowest rank (jaybenne_amd.h)
+            _lib.check(md.lib.jb_defrag_policy(pkg.ctx, md.handle, C.byref(md.sv), events, 1, C.byref(sorted_)))
+            if md.comm.allreduce_max_float(float(sorted_.value)) > 0.0:
+                _lib.check(md.lib.jb_defrag_policy(pkg.ctx, md.handle, C.byref(md.sv), events, 2, C.byref(sorted_)))
+            else:
+                sorted_.value = 0
+        if sorted_.value:
+            md.defrags += 1
+            md._steps_since_defrag = 0
+    elif md.defrag_interval > 0 and md._steps_since_defrag >= md.defrag_interval:
+        DefragParticles(md)
+        md._steps_since_defrag = 0
