@@ -34,7 +34,8 @@ typedef enum jb_status {
   JB_ERR_INVALID = -1,   /* PARTHENON_REQUIRE / PARTHENON_FAIL conditions of the reference */
   JB_ERR_HIP = -2,
   JB_ERR_CAPACITY = -3,
-  JB_ERR_UNSUPPORTED = -4
+  JB_ERR_UNSUPPORTED = -4,
+  JB_ERR_INVARIANT = -5  /* checked library: a transport invariant was violated (jb_invariant_report) */
 } jb_status;
 
 enum { JB_BC_PERIODIC = 0, JB_BC_REFLECT = 1, JB_BC_OUTFLOW = 2 }; /* <parthenon/swarm> i/ox?_bc */
@@ -507,6 +508,65 @@ typedef struct jb_step_report {
 jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, double t_start,
                                   double dt, uint64_t *next_id, uint32_t *cycle, int32_t *prefix_dev,
                                   const jb_rank_comm *comm, jb_step_report *report);
+
+/* ---- transport invariants (checked library) -- the reference's PARTHENON_DEBUG_REQUIREs of the
+ * tracking loop and of SampleDDMCBlockFace, evaluated on every pass (jaybenne_amd/csrc/jb_invariants.hpp).
+ * `make -C jaybenne_amd/csrc checked` builds libjaybenne_amd_checked.so from the same sources with
+ * -DJB_INVARIANTS; a host selects it instead of libjaybenne_amd.so (Python: JAYBENNE_AMD_LIB).  The
+ * release library exports the same symbols: jb_invariants_enabled() = 0 there and the other two return
+ * JB_ERR_UNSUPPORTED.
+ * Status policy of the checked library: tasks accumulate, steps report.  A task keeps its usual status
+ * and only counts; jb_radiation_step returns JB_ERR_INVARIANT when the violation count rose during the
+ * call, and jb_last_error() then quotes the reference's message for the first violation to claim the
+ * record.  jb_exchange carries each rank's violations since its last exchange in its row of the call's
+ * first all-gather: when any rank has one, EVERY rank returns JB_ERR_INVARIANT from that call, before the
+ * payload exchange, and jb_radiation_step_ranks returns it too -- no rank is left in a collective.  The
+ * counts are per process and device, shared by its contexts.  A violating photon is never used as an index
+ * (k_ddmc_q, whose queues have no path that drops a photon, counts it and goes on): it leaves the tracking
+ * loop untallied.
+ * POSITION / INDEX at the top of every event pass and EVENT_OFF_BLOCK at the block exits of k_transport,
+ * k_imc_cell, k_ddmc_all, k_ddmc_q and k_hybrid (cell-local kernels in their own coordinates); FACE_SAMPLE
+ * in k_block_face; DDMC_CLASS; SWARM after SourcePhotons' fill, after an unpack of arrivals, on entry to
+ * every transport task (indices not checked where arrivals may carry their sender's) and in
+ * jb_verify_swarm. */
+enum {
+  JB_INV_POSITION = 0,        /* inside its block at the top of a tracking pass (transport.cpp:100-105) */
+  JB_INV_INDEX = 1,           /* cell indices in the block's interior (transport.cpp:106-111) */
+  JB_INV_EVENT_OFF_BLOCK = 2, /* no absorption / scattering on the step that leaves the block (:152) */
+  JB_INV_FACE_SAMPLE = 3,     /* inside its block after block-face resampling (sample_ddmc_bface.cpp:229) */
+  JB_INV_DDMC_CLASS = 4,      /* class record == the cell's own DDMC step record (after k_ddmc_pack) */
+  JB_INV_SWARM = 5,           /* sweep over the live photons (jb_verify_swarm and the task entries) */
+  JB_INV_NKINDS = 6
+};
+enum {  /* kernel families whose checks count lane-passes */
+  JB_INV_FAM_TRANSPORT = 0,   /* k_transport (x-space tracking: IMC, DDMC, packed hybrid) */
+  JB_INV_FAM_IMC_CELL = 1,    /* k_imc_cell */
+  JB_INV_FAM_DDMC_ALL = 2,    /* k_ddmc_all */
+  JB_INV_FAM_DDMC_Q = 3,      /* k_ddmc_q */
+  JB_INV_FAM_HYBRID = 4,      /* k_hybrid */
+  JB_INV_FAM_BLOCK_FACE = 5,  /* k_block_face */
+  JB_INV_FAM_DDMC_CLASS = 6,  /* the DDMC_CLASS sweep (cells) */
+  JB_INV_FAM_SWARM = 7,       /* the SWARM sweep (photon slots) */
+  JB_INV_NFAMILIES = 8
+};
+typedef struct jb_invariant_report {
+  int64_t evaluated[JB_INV_NKINDS];   /* checks made per kind (POSITION / INDEX: one per lane-pass) */
+  int64_t violated[JB_INV_NKINDS];    /* ... and failed */
+  int64_t passes[JB_INV_NFAMILIES];   /* lane-passes (photons or cells) checked per kernel family */
+  /* the first violation since the last reset (valid when has_first) */
+  int32_t has_first, first_kind, first_family, first_block;
+  int64_t first_slot, first_id;       /* swarm slot (-1: a cell) and creation index (-1: unknown) */
+  int32_t first_ip, first_jp, first_kp, first_axis;  /* first_axis: 0..2, the axis that failed */
+  double first_x, first_y, first_z;
+} jb_invariant_report;
+int jb_invariants_enabled(void);
+/* The counts since the last reset (synchronises the context's stream); reset != 0 zeroes them after. */
+jb_status jb_invariant_report_get(jb_context *ctx, jb_invariant_report *report, int reset);
+/* The SWARM sweep, now, over slots [0, swarm->n) of a swarm whose cycle is [t_start, t_end] (live
+ * photons: t <= t_end).  *report (may be NULL) receives the counts of this sweep alone; they are added
+ * to the running counts too.  JB_COMPLETE when the swarm is clean, JB_ERR_INVARIANT when it is not. */
+jb_status jb_verify_swarm(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, double t_start,
+                          double t_end, jb_invariant_report *report);
 
 /* ---- trace ranges -- the reference's Kokkos::Profiling::pushRegion("Jaybenne::Timestep") ...
  * popRegion() and "Jaybenne::TransportLoop" (jaybenne.cpp:87,115,127,145).  Every task entry point

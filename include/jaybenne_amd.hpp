@@ -44,7 +44,13 @@ struct Error : std::runtime_error {
   Error(jb_status st, const std::string &what) : std::runtime_error(what), status(st) {}
 };
 
+// the checked library (libjaybenne_amd_checked.so): a step that violated a transport invariant
+struct InvariantError : Error {
+  using Error::Error;
+};
+
 inline TaskStatus Check(jb_status st) {
+  if (st == JB_ERR_INVARIANT) throw InvariantError(st, jb_last_error());
   if (st < 0) throw Error(st, jb_last_error());
   return st == JB_ITERATE ? TaskStatus::iterate
                           : (st == JB_INCOMPLETE ? TaskStatus::incomplete : TaskStatus::complete);
@@ -598,6 +604,15 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt,
   md->events += rep.events;
   DefragAfterStep(md, rep.events);
   return TaskStatus::complete;
+}
+
+// ---- transport invariants: the checked library's counts (include/jaybenne_amd.h) ----------------------
+inline bool InvariantsEnabled() { return jb_invariants_enabled() == 1; }
+// throws Error(JB_ERR_UNSUPPORTED) under the release library
+inline jb_invariant_report InvariantReport(MeshData *md, bool reset = false) {
+  jb_invariant_report r{};
+  Check(jb_invariant_report_get(md->ctx(), &r, reset ? 1 : 0));
+  return r;
 }
 
 }  // namespace jaybenne_amd

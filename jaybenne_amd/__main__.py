@@ -58,15 +58,26 @@ def main(argv=None) -> int:
     print(f"problem {drv.mcb.problem_id}: {drv.mesh.ndim}-D, {drv.mesh.nblocks} meshblocks, "
           f"levels {sorted(set(drv.mesh.blk_level.tolist()))}, {drv.md.n} photons")
     t0 = time.perf_counter()
-    while drv.time < drv.tlim:
-        n0, e0 = drv.md.n, drv.md.events
-        c0 = time.perf_counter()
-        drv.Step()
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - c0
-        print(f"cycle={drv.ncycle} time={drv.time:.6e} dt={drv.dt:.6e} photons={drv.md.n} "
-              f"histories/s={n0 / dt:.3e} events/s={(drv.md.events - e0) / dt:.3e}")
+    from ._lib import JB_ERR_INVARIANT, JaybenneError
+    checked = drv.md.invariants_enabled()   # the checked library (JAYBENNE_AMD_LIB): report at exit
+    try:
+        while drv.time < drv.tlim:
+            n0, e0 = drv.md.n, drv.md.events
+            c0 = time.perf_counter()
+            drv.Step()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - c0
+            print(f"cycle={drv.ncycle} time={drv.time:.6e} dt={drv.dt:.6e} photons={drv.md.n} "
+                  f"histories/s={n0 / dt:.3e} events/s={(drv.md.events - e0) / dt:.3e}")
+    except JaybenneError as e:
+        if not (checked and e.status == JB_ERR_INVARIANT):
+            raise
+        print(f"invariants: {drv.md.invariant_report()}")
+        print(f"TEST FAILED: {e}", file=sys.stderr)
+        return 3
     print(f"walltime used = {time.perf_counter() - t0:.2f} s")
+    if checked:
+        print(f"invariants: {drv.md.invariant_report()}")
     tally = drv.md.get_field("tally")
     if drv.mcb.problem_id.startswith("inf"):
         from . import constants

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JAYBENNE_AMD_LIB") or os.path.join(_HERE, "libjaybenne_amd.so")
 
 JB_COMPLETE, JB_ITERATE, JB_INCOMPLETE = 0, 1, 2
-JB_ERR_INVALID, JB_ERR_HIP, JB_ERR_CAPACITY, JB_ERR_UNSUPPORTED = -1, -2, -3, -4
+JB_ERR_INVALID, JB_ERR_HIP, JB_ERR_CAPACITY, JB_ERR_UNSUPPORTED, JB_ERR_INVARIANT = -1, -2, -3, -4, -5
 JB_SOURCE_THERMAL, JB_SOURCE_EMISSION = 0, 1
 JB_STRATEGY_UNIFORM, JB_STRATEGY_ENERGY = 0, 1
 JB_ST_ACTIVE, JB_ST_ABSORBED, JB_ST_ESCAPED, JB_ST_OUTGOING, JB_ST_OUTGOING_ABSORBED = 0, 1, 2, 3, 4
@@ -116,6 +116,31 @@ class StepReport(C.Structure):
                 ("sent", C.c_int64), ("received", C.c_int64), ("events", C.c_int64)]
 
 
+# jb_invariant_report (include/jaybenne_amd.h): the checked library's counts
+INV_KINDS = ("POSITION", "INDEX", "EVENT_OFF_BLOCK", "FACE_SAMPLE", "DDMC_CLASS", "SWARM")
+INV_FAMILIES = ("transport", "imc_cell", "ddmc_all", "ddmc_q", "hybrid", "block_face", "ddmc_class", "swarm")
+
+
+class InvariantReport(C.Structure):
+    _fields_ = [("evaluated", C.c_int64 * len(INV_KINDS)), ("violated", C.c_int64 * len(INV_KINDS)),
+                ("passes", C.c_int64 * len(INV_FAMILIES)),
+                ("has_first", C.c_int32), ("first_kind", C.c_int32), ("first_family", C.c_int32),
+                ("first_block", C.c_int32), ("first_slot", C.c_int64), ("first_id", C.c_int64),
+                ("first_ip", C.c_int32), ("first_jp", C.c_int32), ("first_kp", C.c_int32),
+                ("first_axis", C.c_int32), ("first_x", C.c_double), ("first_y", C.c_double),
+                ("first_z", C.c_double)]
+
+    def as_dict(self) -> dict:
+        d = {"evaluated": dict(zip(INV_KINDS, self.evaluated)), "violated": dict(zip(INV_KINDS, self.violated)),
+             "passes": dict(zip(INV_FAMILIES, self.passes)), "first": None}
+        if self.has_first:
+            d["first"] = {"kind": INV_KINDS[self.first_kind], "family": INV_FAMILIES[self.first_family],
+                          "block": self.first_block, "slot": self.first_slot, "id": self.first_id,
+                          "ijk": (self.first_ip, self.first_jp, self.first_kp), "axis": self.first_axis,
+                          "x": (self.first_x, self.first_y, self.first_z)}
+        return d
+
+
 # every entry point include/jaybenne_amd.h declares: name -> (restype, argtypes)
 _vp, _i64, _f64, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
 PROTOTYPES = {
@@ -165,6 +190,9 @@ PROTOTYPES = {
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _vp]),
     "jb_radiation_step_ranks": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint32), _vp, C.POINTER(RankComm), C.POINTER(StepReport)]),
+    "jb_invariants_enabled": (_int, []),
+    "jb_invariant_report_get": (_int, [_vp, C.POINTER(InvariantReport), _int]),
+    "jb_verify_swarm": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64, C.POINTER(InvariantReport)]),
     "jb_range_push": (_int, [C.c_char_p]),
     "jb_range_pop": (_int, []),
     "jb_ranges_enabled": (_int, []),

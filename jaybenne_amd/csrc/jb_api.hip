@@ -61,7 +61,9 @@ struct jb_context {
   bool scratch_alloc_failed = false;          // set by ensure_scratch when hipMalloc itself said no
   std::vector<unsigned long long> xch_matrix;  // jb_exchange: the rank x rank record counts (host copy)
   std::vector<long long> xch_tab;             // ... this rank's send / receive counts and offsets
-  unsigned long long xch_room[3] = {0, 0, 0}; // ... and its room: send buffer, receive buffer, free swarm slots (records)
+  unsigned long long xch_room[4] = {0, 0, 0, 0}; // ... and its room: send buffer, receive buffer, free swarm slots (records)
+                                              // | (checked build) this rank's invariant violations since its last exchange
+  long long inv_reported = 0;                 // (checked build) the violation count the last jb_exchange reported
   size_t scratch_words = 0;
   // jb_radiation_step_ranks: the hand-off record buffers (JB_RECORD_WORDS words per record) and the buffer of
   // the step's first all-gather ([status | counts per global block] of this rank, then every rank's)
@@ -195,6 +197,143 @@ static int grid_for(const jb_context *ctx, long long n, int per_cu = 8) {
   return (int)blocks;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Transport invariants (jb_invariants.hpp).  The checked library (-DJB_INVARIANTS, `make checked`) counts
+// into one buffer per process and device, allocated by the first jb_initialize on that device; the
+// release library has none of this and answers the three entry points below with "not built".
+#ifdef JB_INVARIANTS
+constexpr int kInvDevices = 64;
+static unsigned long long *g_inv_d[kInvDevices] = {};
+
+static jb_status inv_setup(int device) {
+  if (device < 0 || device >= kInvDevices) return fail(JB_ERR_UNSUPPORTED, "checked library: device %d", device);
+  if (g_inv_d[device]) return JB_COMPLETE;
+  unsigned long long *p = nullptr;
+  JB_HIP(hipMalloc(&p, inv::kBufferWords * sizeof(unsigned long long)));
+  JB_HIP(hipMemset(p, 0, inv::kBufferWords * sizeof(unsigned long long)));
+  JB_HIP(hipMemcpyToSymbol(HIP_SYMBOL(inv::jb_inv_buf), &p, sizeof p));
+  g_inv_d[device] = p;
+  return JB_COMPLETE;
+}
+
+// the counts as a report (stripes summed; POSITION / INDEX are evaluated once per lane-pass of a tracking
+// family, so their evaluated counts are those families' pass counts)
+static jb_status inv_read(jb_context *ctx, jb_invariant_report *r) {
+  std::vector<unsigned long long> h(inv::kBufferWords);
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  JB_HIP(hipMemcpy(h.data(), g_inv_d[ctx->device], h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  memset(r, 0, sizeof *r);
+  auto sum = [&](int base, int index) {
+    unsigned long long s = 0;
+    for (int q = 0; q < inv::kStripes; ++q) s += h[base + index * inv::kCountWords + q * inv::kStripeWords];
+    return (int64_t)s;
+  };
+  for (int k = 0; k < JB_INV_NKINDS; ++k) {
+    r->evaluated[k] = sum(inv::kEvalBase, k);
+    r->violated[k] = sum(inv::kViolBase, k);
+  }
+  for (int f = 0; f < JB_INV_NFAMILIES; ++f) r->passes[f] = sum(inv::kPassBase, f);
+  for (int f = JB_INV_FAM_TRANSPORT; f <= JB_INV_FAM_HYBRID; ++f) {
+    r->evaluated[JB_INV_POSITION] += r->passes[f];
+    r->evaluated[JB_INV_INDEX] += r->passes[f];
+  }
+  const unsigned long long *rec = h.data() + inv::kRecord;
+  r->has_first = h[inv::kClaim] != 0ull;
+  if (r->has_first) {
+    r->first_kind = (int32_t)rec[inv::R_KIND];
+    r->first_family = (int32_t)rec[inv::R_FAMILY];
+    r->first_block = (int32_t)(long long)rec[inv::R_BLOCK];
+    r->first_slot = (int64_t)rec[inv::R_SLOT];
+    r->first_id = (int64_t)rec[inv::R_ID];
+    r->first_ip = (int32_t)(long long)rec[inv::R_IP];
+    r->first_jp = (int32_t)(long long)rec[inv::R_JP];
+    r->first_kp = (int32_t)(long long)rec[inv::R_KP];
+    memcpy(&r->first_x, &rec[inv::R_X], sizeof(double));
+    memcpy(&r->first_y, &rec[inv::R_Y], sizeof(double));
+    memcpy(&r->first_z, &rec[inv::R_Z], sizeof(double));
+    r->first_axis = (int32_t)rec[inv::R_AXIS];
+  }
+  return JB_COMPLETE;
+}
+
+static int64_t inv_total(const jb_invariant_report &r) {
+  int64_t v = 0;
+  for (int k = 0; k < JB_INV_NKINDS; ++k) v += r.violated[k];
+  return v;
+}
+
+static jb_status inv_violations(jb_context *ctx, int64_t *out) {
+  jb_invariant_report r;
+  const jb_status st = inv_read(ctx, &r);
+  *out = st == JB_COMPLETE ? inv_total(r) : 0;
+  return st;
+}
+
+// JB_ERR_INVARIANT with the reference's message for the first violation
+static jb_status inv_fail(jb_context *ctx, int64_t n_new, const char *who) {
+  jb_invariant_report r;
+  if (inv_read(ctx, &r) != JB_COMPLETE || !r.has_first)
+    return fail(JB_ERR_INVARIANT, "%s: %lld transport invariant violation(s)", who, (long long)n_new);
+  static const char *const kPosition[3] = {"Particle initially outside block X1 domain!",
+                                           "Particle initially outside block X2 domain!",
+                                           "Particle initially outside block x3 domain!"};
+  static const char *const kIndex[3] = {"Particle initially outside X1 logical bnds!",
+                                        "Particle initially outside X2 logical bnds!",
+                                        "Particle initially outside X3 logical bnds!"};
+  const int axis = r.first_axis >= 0 && r.first_axis < 3 ? r.first_axis : 0;
+  const char *msg = "transport invariant violated";
+  switch (r.first_kind) {
+  case JB_INV_POSITION: msg = kPosition[axis]; break;
+  case JB_INV_INDEX: msg = kIndex[axis]; break;
+  case JB_INV_EVENT_OFF_BLOCK: msg = "Absorption/scattering event off block!"; break;
+  case JB_INV_FACE_SAMPLE: msg = "Particle sampled outside of meshblock!"; break;
+  case JB_INV_DDMC_CLASS: msg = "DDMC class record differs from the cell's own step record"; break;
+  case JB_INV_SWARM: msg = "swarm invariant violated (block, indices, position, status, w, e or t)"; break;
+  }
+  return fail(JB_ERR_INVARIANT, "%s: %s (%lld violation(s); first: family %d, block %d, slot %lld, id %lld, "
+              "ijk %d %d %d, x %.17g %.17g %.17g)", who, msg, (long long)n_new, r.first_family, r.first_block,
+              (long long)r.first_slot, (long long)r.first_id, r.first_ip, r.first_jp, r.first_kp, r.first_x,
+              r.first_y, r.first_z);
+}
+
+// the SWARM sweep over slots [first, last), on the context's stream
+static jb_status inv_sweep(jb_context *ctx, const DevMesh &M, const DevSwarm &S, long long first, long long last,
+                           double t_end, bool check_index) {
+  if (last <= first) return JB_COMPLETE;
+  hipLaunchKernelGGL(k_inv_swarm, dim3(grid_for(ctx, last - first)), dim3(kBlock), 0, ctx->stream, M, S, first,
+                     last, t_end, check_index ? 1 : 0);
+  JB_HIP(hipGetLastError());
+  return JB_COMPLETE;
+}
+#endif
+
+extern "C" int jb_invariants_enabled(void) {
+#ifdef JB_INVARIANTS
+  return 1;
+#else
+  return 0;
+#endif
+}
+
+extern "C" jb_status jb_invariant_report_get(jb_context *ctx, jb_invariant_report *report, int reset) {
+#ifdef JB_INVARIANTS
+  if (!ctx || !report) return fail(JB_ERR_INVALID, "jb_invariant_report_get: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  const jb_status st = inv_read(ctx, report);
+  if (st != JB_COMPLETE) return st;
+  if (reset) {   // (on the context's stream: the check kernels run there)
+    JB_HIP(hipMemsetAsync(g_inv_d[ctx->device], 0, inv::kBufferWords * sizeof(unsigned long long), ctx->stream));
+    JB_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->inv_reported = 0;
+  }
+  return JB_COMPLETE;
+#else
+  (void)ctx; (void)report; (void)reset;
+  return fail(JB_ERR_UNSUPPORTED, "jb_invariant_report_get: this is the release library; the transport invariants "
+              "are checked by libjaybenne_amd_checked.so (make -C jaybenne_amd/csrc checked)");
+#endif
+}
+
 // (slack: small tables grow with the run and are re-requested often; the sort's particle records --
 // 128 bytes per photon -- are sized exactly: 25 % on top of 12.8 GB is memory a run near the card's
 // capacity may not have)
@@ -317,6 +456,10 @@ extern "C" jb_status jb_initialize(const jb_params *params, const jb_eos *eos,
     hipLaunchKernelGGL(k_rcp_refined, dim3(1), dim3(1), 0, 0, ctx->dp.c, (double *)ctx->counters_d);
     JB_HIP(hipMemcpy(&ctx->dp.rc, ctx->counters_d, sizeof(double), hipMemcpyDeviceToHost));
     JB_HIP(hipMemset(ctx->counters_d, 0, sizeof(double)));
+#ifdef JB_INVARIANTS
+    const jb_status ist = inv_setup(device);
+    if (ist != JB_COMPLETE) return ist;
+#endif
     return JB_COMPLETE;
   };
   const jb_status st = init_device_state();
@@ -736,6 +879,10 @@ extern "C" jb_status jb_update_derived_transport_fields(jb_context *ctx, jb_mesh
       if (M.ndim == 1) hipLaunchKernelGGL(k_ddmc_pack<1>, dim3(gp), dim3(kBlock), 0, ctx->stream, M, ctx->dp, mc);
       else if (M.ndim == 2) hipLaunchKernelGGL(k_ddmc_pack<2>, dim3(gp), dim3(kBlock), 0, ctx->stream, M, ctx->dp, mc);
       else hipLaunchKernelGGL(k_ddmc_pack<3>, dim3(gp), dim3(kBlock), 0, ctx->stream, M, ctx->dp, mc);
+#ifdef JB_INVARIANTS
+      if (M.ddmc_code && M.ddmc_class)   // (checked build) DDMC_CLASS
+        hipLaunchKernelGGL(k_inv_ddmc_class, dim3(gp), dim3(kBlock), 0, ctx->stream, M, mc);
+#endif
     }
   }
   JB_HIP(hipGetLastError());
@@ -835,6 +982,18 @@ extern "C" jb_status jb_source_photons_fill_range(jb_context *ctx, jb_mesh *mesh
                        first_in_block_host ? (const long long *)(tab_d + 3 * M.nblocks) : (const long long *)nullptr,
                        total);
   JB_HIP(hipGetLastError());
+#ifdef JB_INVARIANTS
+  {  // (checked build) SWARM over the slots just filled
+    long long lo = swarm->capacity, hi = 0;
+    for (int b = 0; b < M.nblocks; ++b)
+      if (nper[b] > 0) {
+        lo = slot_base_host[b] < lo ? slot_base_host[b] : lo;
+        hi = slot_base_host[b] + nper[b] > hi ? slot_base_host[b] + nper[b] : hi;
+      }
+    st = inv_sweep(ctx, M, dev_swarm(swarm), lo, hi, t_start + dt, true);
+    if (st != JB_COMPLETE) return st;
+  }
+#endif
   JB_HIP(hipStreamSynchronize(ctx->stream));  // tab lives on this stack frame
   return JB_COMPLETE;
 }
@@ -1156,6 +1315,10 @@ static jb_status transport_impl(jb_context *ctx, jb_mesh *mesh, const jb_swarm_v
   if (first == last) return JB_COMPLETE;
   const DevSwarm S = dev_swarm(swarm);
   const bool tl = tally != 0;
+#ifdef JB_INVARIANTS
+  st = inv_sweep(ctx, M, S, first, last, t_start + dt, false);   // (checked build) SWARM on entry (k_inv_swarm)
+  if (st != JB_COMPLETE) return st;
+#endif
   // (jb_defrag_policy: the time of the tracking kernels of this cycle, per event)
   hipEvent_t ev_stop = nullptr;
   if (ctx->tev_used + 2 <= 2 * kTransportEventPairs) {
@@ -1195,6 +1358,35 @@ extern "C" jb_status jb_transport_photons_ddmc(jb_context *ctx, jb_mesh *mesh,
                                                int64_t first, int64_t last, int fuse_census_tally) {
   JB_RANGE("Jaybenne::TransportPhotons_DDMC");
   return transport_impl(ctx, mesh, swarm, t_start, dt, first, last, fuse_census_tally, true);
+}
+
+extern "C" jb_status jb_verify_swarm(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, double t_start,
+                                     double t_end, jb_invariant_report *report) {
+#ifdef JB_INVARIANTS
+  if (!ctx || !mesh) return fail(JB_ERR_INVALID, "jb_verify_swarm: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  jb_status st = check_swarm(swarm, "jb_verify_swarm");
+  if (st != JB_COMPLETE) return st;
+  if (!(t_start <= t_end)) return fail(JB_ERR_INVALID, "jb_verify_swarm: t_start > t_end");
+  jb_invariant_report before, after;
+  if ((st = inv_read(ctx, &before)) != JB_COMPLETE) return st;
+  if ((st = inv_sweep(ctx, mesh->dm, dev_swarm(swarm), 0, swarm->n, t_end, true)) != JB_COMPLETE) return st;
+  if ((st = inv_read(ctx, &after)) != JB_COMPLETE) return st;
+  jb_invariant_report d = after;   // this sweep's counts; its first violation if the claim was free before it
+  for (int k = 0; k < JB_INV_NKINDS; ++k) {
+    d.evaluated[k] -= before.evaluated[k];
+    d.violated[k] -= before.violated[k];
+  }
+  for (int f = 0; f < JB_INV_NFAMILIES; ++f) d.passes[f] -= before.passes[f];
+  if (before.has_first) d.has_first = 0;
+  if (report) *report = d;
+  const int64_t n_new = inv_total(d);
+  return n_new > 0 ? inv_fail(ctx, n_new, "jb_verify_swarm") : JB_COMPLETE;
+#else
+  (void)ctx; (void)mesh; (void)swarm; (void)t_start; (void)t_end; (void)report;
+  return fail(JB_ERR_UNSUPPORTED, "jb_verify_swarm: this is the release library; the transport invariants are "
+              "checked by libjaybenne_amd_checked.so (make -C jaybenne_amd/csrc checked)");
+#endif
 }
 
 extern "C" const char *jb_last_transport_variant(const jb_mesh *mesh) {
@@ -1650,6 +1842,12 @@ extern "C" jb_status jb_unpack_incoming(jb_context *ctx, jb_mesh *mesh, jb_swarm
                      mesh->dm, dev_swarm(swarm), (long long)swarm->n, (const long long *)records_dev,
                      (long long)nrecords);
   JB_HIP(hipGetLastError());
+#ifdef JB_INVARIANTS
+  {  // (checked build) SWARM over the arrivals (their indices are their sender's: see k_inv_swarm)
+    const jb_status ist = inv_sweep(ctx, mesh->dm, dev_swarm(swarm), swarm->n, swarm->n + nrecords, DBL_MAX, false);
+    if (ist != JB_COMPLETE) return ist;
+  }
+#endif
   swarm->n += nrecords;
   return JB_COMPLETE;
 }
@@ -1688,10 +1886,15 @@ extern "C" jb_status jb_exchange(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *
   if (st != JB_COMPLETE) return st;
   if (first < 0 || last > swarm->n || first > last) return fail(JB_ERR_INVALID, "bad particle range");
   if (rank < 0 || rank >= nranks) return fail(JB_ERR_INVALID, "rank outside [0, nranks)");
-  if (nranks < mesh->nranks_seen || nranks + 3 > kRankEnd - kRankBase)
+#ifdef JB_INVARIANTS
+  constexpr int kRoomWords = 4;   // (checked build) + this rank's invariant violations since its last exchange
+#else
+  constexpr int kRoomWords = 3;
+#endif
+  if (nranks < mesh->nranks_seen || nranks + kRoomWords > kRankEnd - kRankBase)
     return fail(JB_ERR_INVALID, "nranks = %d does not cover the owners in the mesh view", nranks);
   *nsent = 0; *nreceived = 0; *moved_anywhere = 0;
-  const int row = nranks + 3;   // what a rank contributes to the all-gather: counts | send, receive, swarm room
+  const int row = nranks + kRoomWords;   // what a rank contributes to the all-gather: counts | send, receive, swarm room
   // 1. records per destination rank, counted on the device ...
   unsigned long long *per_rank = ctx->counters_d + kRankBase;
   JB_HIP(hipMemsetAsync(per_rank, 0, sizeof(unsigned long long) * nranks, ctx->stream));
@@ -1706,7 +1909,17 @@ extern "C" jb_status jb_exchange(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *
   ctx->xch_room[0] = (unsigned long long)(send_dev ? send_capacity : 0);
   ctx->xch_room[1] = (unsigned long long)(recv_dev ? recv_capacity : 0);
   ctx->xch_room[2] = (unsigned long long)(swarm->capacity - swarm->n);
-  JB_HIP(hipMemcpyAsync(per_rank + nranks, ctx->xch_room, 3 * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+#ifdef JB_INVARIANTS
+  {  // the violations since this rank's last exchange travel in its row: every rank sees every rank's
+    int64_t tot = 0;
+    JB_HIP(hipStreamSynchronize(ctx->stream));   // (the record counts above are not read back: only the kernels' end)
+    if (inv_violations(ctx, &tot) != JB_COMPLETE) tot = ctx->inv_reported + 1;   // (unreadable: reported as one)
+    ctx->xch_room[3] = (unsigned long long)(tot - ctx->inv_reported);
+    ctx->inv_reported = tot;
+  }
+#endif
+  JB_HIP(hipMemcpyAsync(per_rank + nranks, ctx->xch_room, kRoomWords * sizeof(unsigned long long), hipMemcpyHostToDevice,
+                        ctx->stream));
   // 2. ... gathered from every rank straight from that buffer (no read-back in front of the collective):
   // the rank x rank matrix carries this rank's receive sizes AND the answer to "did anything move
   // anywhere" (the completion test of jaybenne.cpp:130-131 needs no collective of its own) ...
@@ -1737,6 +1950,14 @@ extern "C" jb_status jb_exchange(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *
   }
   *moved_anywhere = total;
   *nsent = mine_out; *nreceived = mine_in;
+#ifdef JB_INVARIANTS
+  {  // (checked build) the same verdict on every rank, before anything else is exchanged: JB_ERR_INVARIANT when any
+     // rank has had a violation since its last exchange (steps report: jb_radiation_step_ranks returns it too)
+    unsigned long long v = 0;
+    for (int q = 0; q < nranks; ++q) v += ctx->xch_matrix[(size_t)q * row + nranks + 3];
+    if (v != 0) return inv_fail(ctx, (int64_t)v, "jb_exchange");
+  }
+#endif
   // (every rank looks at every rank's diagonal: the same verdict everywhere)
   for (int q = 0; q < nranks; ++q)
     if (cnt(q, q) != 0) return fail(JB_ERR_INVALID, "jb_exchange: rank %d hands particles to itself", q);
@@ -1773,6 +1994,11 @@ extern "C" jb_status jb_exchange(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *
                        mesh->dm, dev_swarm(swarm), (long long)swarm->n, (const long long *)recv_dev,
                        (long long)mine_in);
     JB_HIP(hipGetLastError());
+#ifdef JB_INVARIANTS
+    // (checked build) SWARM over the arrivals (their indices are their sender's: see k_inv_swarm)
+    if (inv_sweep(ctx, mesh->dm, dev_swarm(swarm), swarm->n, swarm->n + mine_in, DBL_MAX, false) != JB_COMPLETE)
+      return JB_ERR_HIP;
+#endif
     swarm->n += mine_in;
   }
   return JB_COMPLETE;
@@ -1907,9 +2133,8 @@ extern "C" jb_status jb_fill_cells(jb_context *ctx, jb_mesh *mesh, int field, in
 // ------------------------------------------------------------------------------------------------
 // RadiationStep for a mesh held entirely by this rank: the task list of jaybenne.cpp:104-138 with
 // the iterate-sublist collapsed to one launch (every block crossing is resolved in flight).
-extern "C" jb_status jb_radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm,
-                                       double t_start, double dt, uint64_t *next_id, uint32_t *cycle,
-                                       int32_t *prefix_dev) {
+static jb_status radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, double t_start, double dt,
+                                uint64_t *next_id, uint32_t *cycle, int32_t *prefix_dev) {
   if (!ctx || !mesh || !swarm || !next_id || !cycle) return fail(JB_ERR_INVALID, "null argument");
   const DevMesh &M = mesh->dm;
   if (M.nblocks != M.nblocks_total || mesh->nranks_seen != 1)
@@ -1963,6 +2188,26 @@ extern "C" jb_status jb_radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_
     if (st != JB_COMPLETE) return st;
   }
   return jb_update_fluid(ctx, mesh);
+}
+
+extern "C" jb_status jb_radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm,
+                                       double t_start, double dt, uint64_t *next_id, uint32_t *cycle,
+                                       int32_t *prefix_dev) {
+#ifdef JB_INVARIANTS
+  // (checked build) tasks accumulate, steps report: JB_ERR_INVARIANT when the count rose during the step
+  if (!ctx) return fail(JB_ERR_INVALID, "null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  int64_t v0 = 0, v1 = 0;
+  jb_status st = inv_violations(ctx, &v0);
+  if (st != JB_COMPLETE) return st;
+  st = radiation_step(ctx, mesh, swarm, t_start, dt, next_id, cycle, prefix_dev);
+  const jb_status ist = inv_violations(ctx, &v1);
+  if (ist != JB_COMPLETE) return ist;
+  if (v1 > v0) return inv_fail(ctx, v1 - v0, "jb_radiation_step");
+  return st;
+#else
+  return radiation_step(ctx, mesh, swarm, t_start, dt, next_id, cycle, prefix_dev);
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------

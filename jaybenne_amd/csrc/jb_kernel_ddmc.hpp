@@ -701,7 +701,18 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD) JB_DDMC_AL
           if constexpr (NDIM == 1) mir = (tab && (cd & kCodeMirror) != 0u) ? !mir : mir;
           ls = (gl && !tab) ? DS_RELOC : ls;
         }
-        const bool live = run && !ghost;
+        // (checked build) POSITION / INDEX: in the event loop a photon's position is its cell, named by its record
+        // number (the step function places it in the cell only behind the loop), so the condition is that the
+        // record number of a lane about to step names an interior cell of a resident block.  A violating lane
+        // leaves untallied.
+        JB_INV_STMT(bool inv_bad = false;)
+        JB_INV_STMT({
+          int ib = -1, ii = 0, ij = 0, ik = 0;
+          const bool idx = inv::cell_interior(M, rec, ib, ii, ij, ik);
+          JB_INV_PASS_PRED(JB_INV_FAM_DDMC_ALL, run && !ghost, true, idx, 0, ib, ii, ij, ik, 0.0, 0.0, 0.0, n, S.id,
+                           { inv_bad = true; ls = DS_IDLE; });
+        })
+        const bool live = run && !ghost JB_INV_STMT(&& !inv_bad);
         // transport_utils.hpp:184-191
         const double a2 = r.ffaa + r.leak_tot;
         const double cdf_ddmc = a2 + DBL_MIN;
@@ -815,7 +826,15 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD) JB_DDMC_AL
       delta = (xim < r.c1) ? -1 : delta;
       const bool leak = ev && !absorbed && xi < a2 && delta != 0;
       const unsigned long long s4 = s0 * kMul4 + kInc4;
-      if (run && !ghost) {
+      // (checked build) POSITION / INDEX as in the cell-code form above
+      JB_INV_STMT(bool inv_bad = false;)
+      JB_INV_STMT({
+        int ib = -1, ii = 0, ij = 0, ik = 0;
+        const bool idx = inv::cell_interior(M, rec, ib, ii, ij, ik);
+        JB_INV_PASS_PRED(JB_INV_FAM_DDMC_ALL, run && !ghost, true, idx, 0, ib, ii, ij, ik, 0.0, 0.0, 0.0, n, S.id,
+                         { inv_bad = true; ls = DS_IDLE; });
+      })
+      if (run && !ghost JB_INV_STMT(&& !inv_bad)) {
         t = t_new;
         rng.s = leak ? s4 : (ev ? s2 : s1);
         // the leak's two direction uniforms (:217,235,253) are the two draws behind s2: remember where

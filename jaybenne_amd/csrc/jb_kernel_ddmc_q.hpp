@@ -629,6 +629,15 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)
         if constexpr (NDIM == 1) r_mir ^= (tab && (cd & kCodeMirror) != 0u) ? 1u : 0u;
         r_ls = (gl && !tab) ? DS_RELOC : r_ls;
       }
+      // (checked build) POSITION / INDEX as in k_ddmc_all: the record number of a lane about to step names an
+      // interior cell of a resident block.  Counted and recorded; the queue protocol of this kernel has no
+      // path that drops a photon, so a violating lane goes on as in the release build.
+      JB_INV_STMT({
+        int ib = -1, ii = 0, ij = 0, ik = 0;
+        const bool idx = inv::cell_interior(M, r_rec, ib, ii, ij, ik);
+        JB_INV_PASS_PRED(JB_INV_FAM_DDMC_Q, run && !ghost, true, idx, 0, ib, ii, ij, ik, 0.0, 0.0, 0.0, -1, nullptr,
+                         (void)0);
+      })
       const bool live = run && !ghost;
       // transport_utils.hpp:184-191
       const double a2 = r.ffaa + r.leak_tot;

@@ -674,6 +674,15 @@ __global__ void __launch_bounds__(kBlock, PHASE == 0 ? JB_HYBRID_REMAINDER_WAVES
       int nrun = n_virt;
       int thresh = 1;
       while (nrun >= thresh) {
+        // (checked build) POSITION / INDEX of the DDMC loop: the photon's position is its cell here (the step
+        // function keeps it at the cell centre), so the condition is that (b, ip, jp, kp) name an interior cell
+        // of a resident block.  A violating lane leaves untallied.
+        JB_INV_STMT({
+          const int I[3] = {ip, jp, kp}, f3[3] = {M.is, M.js, M.ks}, l3[3] = {M.ie, M.je, M.ke};
+          const bool idx = inv::block_ok(b, M.nblocks) && inv::index_ok(I, f3, l3);
+          JB_INV_PASS_PRED(JB_INV_FAM_HYBRID, ls == HS_VIRT, true, idx, 0, b, ip, jp, kp, 0.0, 0.0, 0.0, n, S.id,
+                           ls = HS_IDLE);
+        })
         Step s;
         if (ls == HS_VIRT) {
           s.t_start = t_start; s.dt = dt; s.vv = vv;
@@ -701,6 +710,8 @@ __global__ void __launch_bounds__(kBlock, PHASE == 0 ? JB_HYBRID_REMAINDER_WAVES
           resample = census;
           if (!on_block_l(ip, jp, kp)) {
             ls = HS_RELOC;  // a leak through a block face: the service phase
+            JB_INV_OFF_BLOCK(JB_INV_FAM_HYBRID, s.is_absorbed, false, b, ip, jp, kp, 0.0, 0.0, 0.0, n, S.id,
+                             ls = HS_IDLE);
           } else if (s.is_absorbed) {  // transport.cpp:157-163
             if (lds_blocks.owned[b] != 0) {
               atomicAdd(&M.edelta[b][cidx_l(kp, jp, ip)], g1(S.w)[n]);
@@ -779,7 +790,19 @@ __global__ void __launch_bounds__(kBlock, PHASE == 0 ? JB_HYBRID_REMAINDER_WAVES
             }
           }
         }
-        if (stepping) {
+        // (checked build) POSITION / INDEX in cell-local coordinates, as in k_imc_cell: |p| <= h on the active
+        // axes, and the byte offset names an interior cell of the lane's block b
+        JB_INV_STMT(bool inv_bad = false;)
+        JB_INV_STMT({
+          int ib = -1, ii = 0, ij = 0, ik = 0, ax = 0;
+          const double pp[3] = {x, y, z}, hh[3] = {cg.hx, cg.hy, cg.hz};
+          const bool pos = inv::local_position_ok(NDIM, pp, hh, ax);
+          const bool idx = inv::cell_interior(M, (unsigned long long)b * (unsigned long long)M.ntot +
+                                                     (unsigned long long)((qoff - hyb_off) >> 3), ib, ii, ij, ik) && ib == b;
+          JB_INV_PASS_PRED(JB_INV_FAM_HYBRID, stepping, pos, idx, ax, b, ii, ij, ik, x, y, z, n, S.id,
+                           { inv_bad = true; ls = HS_IDLE; });
+        })
+        if (stepping JB_INV_STMT(&& !inv_bad)) {
           bool is_absorbed, is_scattered, hit_any;
           imc_step_cell<NDIM, NOABS>(cg, l_sy, l_sz, lam_a_cur, lam_cur, rng, t, x, y, z, vx, vy, vz, qoff,
                                      is_absorbed, is_scattered, hit_any);
@@ -819,6 +842,8 @@ __global__ void __launch_bounds__(kBlock, PHASE == 0 ? JB_HYBRID_REMAINDER_WAVES
         ++st_imc_pass; st_imc_lanes += stepping;
 #endif
         bool crossing = false;  // left its block in this pass
+        // (checked build) POSITION / INDEX in x-space, against the block tables
+        JB_INV_PASS(JB_INV_FAM_HYBRID, ls == HS_IMC, M, b, ip, jp, kp, x, y, z, n, S.id, ls = HS_IDLE);
         if (ls == HS_IMC) {
           bool is_absorbed, is_scattered;
           if constexpr (kLean) {
@@ -846,6 +871,7 @@ __global__ void __launch_bounds__(kBlock, PHASE == 0 ? JB_HYBRID_REMAINDER_WAVES
           }
           if (!on_block_l(ip, jp, kp)) {
             crossing = true;
+            JB_INV_OFF_BLOCK(JB_INV_FAM_HYBRID, is_absorbed, is_scattered, b, ip, jp, kp, x, y, z, n, S.id, (void)0);
           } else if (is_absorbed) {  // transport.cpp:157-163
             if (lds_blocks.owned[b] != 0) {
               atomicAdd(&M.edelta[b][cidx_l(kp, jp, ip)], g1(S.w)[n]);

@@ -162,6 +162,7 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
     cg.dxp = dmin(d0, dmin(d1, d2));
   }
   double lam_a = 0.0, lam_s = 0.0;          // mean free paths of the photon's cell, or the ghost code
+  JB_INV_STMT(bool inv_collided = false;)   // (checked build) the lane's last step ended in a collision
 
   auto fetch_lam = [&]() {
     if constexpr (!NOABS) lam_a = *(gcptr)(lam_abs0 + qoff);
@@ -369,6 +370,8 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
       c_evp += (1ull << 40) + (unsigned long long)(nrun - __popcll(cross_m));
       if (cross_m != 0ull) {
         if (cross) {
+          // (checked build) EVENT_OFF_BLOCK: the step that took the photon into this ghost cell had no collision
+          JB_INV_OFF_BLOCK(JB_INV_FAM_IMC_CELL, inv_collided, false, block_of(), 0, 0, 0, px, py, pz, n, S.id, (void)0);
           const int code = __double2hiint(lam_s);
           if ((code & kGhostTable) == 0) {
             b = block_of();
@@ -398,7 +401,22 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
           }
         }
       }
-      if (stepping) {
+      // (checked build) POSITION / INDEX in this kernel's coordinates, for a lane about to step: the position
+      // relative to the cell centre within the half cell widths, |p| <= h on the active axes, and the byte
+      // offset naming an interior cell of a resident block.  A violating lane leaves untallied.
+      JB_INV_STMT(bool inv_bad = false;)
+      JB_INV_STMT({
+        int ib = -1, ii = 0, ij = 0, ik = 0, ax = 0;
+        const double pp[3] = {px, py, pz}, hh[3] = {cg.hx, cg.hy, cg.hz};
+        const bool pos = inv::local_position_ok(NDIM, pp, hh, ax);
+        const unsigned cell = (qoff % blk_bytes) >> 3;
+        const bool idx = cell < (unsigned)M.ntot &&
+                         inv::cell_interior(M, (unsigned long long)(qoff / blk_bytes) * (unsigned long long)M.ntot + cell,
+                                            ib, ii, ij, ik);
+        JB_INV_PASS_PRED(JB_INV_FAM_IMC_CELL, stepping, pos, idx, ax, ib, ii, ij, ik, px, py, pz, n, S.id,
+                         { inv_bad = true; ls = IS_IDLE; });
+      })
+      if (stepping JB_INV_STMT(&& !inv_bad)) {
         bool is_absorbed, is_scattered, hit_any;
         imc_step_cell<NDIM, NOABS, UNIFORM, kWide>(cg, sy, sz, lam_a, lam_s, rng, drem, px, py, pz, ox, oy, oz, qoff,
                                             is_absorbed, is_scattered, hit_any);
@@ -415,6 +433,7 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
           if (at_face) off = lam_s < 0.0;
         }
         collide = collide && !off;
+        JB_INV_STMT(inv_collided = collide;)
         if (!NOABS && is_absorbed && collide) {  // transport.cpp:157-163
           b = block_of();
           if (M.owned[b]) {

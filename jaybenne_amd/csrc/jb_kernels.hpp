@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "jb_device.hpp"
+#include "jb_invariants.hpp"   // the checked build's JB_INV_* call sites (nothing without JB_INVARIANTS)
 
 namespace jb {
 
@@ -1065,6 +1066,10 @@ __launch_bounds__(kBlock, DDMC ? JB_DDMC_WAVES_PER_SIMD
     while (nrun >= thresh) {
       ++c_pass;
       c_ev += (unsigned int)nrun;
+      // (checked build) POSITION / INDEX against the block tables in global memory: the gray IMC kernels
+      // keep only B.x0 of their block copy current across a face crossing
+      JB_INV_PASS(JB_INV_FAM_TRANSPORT, ls == LS_RUN, M, b, ip, jp, kp, x, y, z, n, S.id,
+                  { ls = LS_IDLE; pend = -1; resample = false; });
       if constexpr (kFastGray) {
         if (ls == LS_RUN) {
           // per-cell mean free paths precomputed by k_fleck: two gathers instead of three, and
@@ -1113,6 +1118,8 @@ __launch_bounds__(kBlock, DDMC ? JB_DDMC_WAVES_PER_SIMD
           }
           if (!on_block(M, ip, jp, kp)) {
             ls = LS_RELOC;  // comm phase: below, for the lanes that need it
+            JB_INV_OFF_BLOCK(JB_INV_FAM_TRANSPORT, is_absorbed, is_scattered, b, ip, jp, kp, x, y, z, n, S.id,
+                             ls = LS_IDLE);
           } else if (is_absorbed) {  // transport.cpp:157-163
             if (M.owned[b]) {
               atomicAdd(&M.edelta[b][cidx(M, kp, jp, ip)], g1(S.w)[n]);
@@ -1239,6 +1246,9 @@ __launch_bounds__(kBlock, DDMC ? JB_DDMC_WAVES_PER_SIMD
         }
 
         if (!on_block(M, ip, jp, kp)) {
+          JB_INV_STMT(bool inv_drop = false;)
+          JB_INV_OFF_BLOCK(JB_INV_FAM_TRANSPORT, s.is_absorbed, s.is_scattered, b, ip, jp, kp, x, y, z, n, S.id,
+                           inv_drop = true);
           bool crossed = false;
           if constexpr (kPackedDdmc) {
             // an IMC step of a hybrid deck through one face into a block of the same size, a
@@ -1268,6 +1278,7 @@ __launch_bounds__(kBlock, DDMC ? JB_DDMC_WAVES_PER_SIMD
             }
             ls = LS_RELOC;  // comm phase: in the service phase
           }
+          JB_INV_STMT(if (inv_drop) { ls = LS_IDLE; pend = -1; resample = false; })
         } else if (s.is_absorbed) {  // transport.cpp:157-163
           if (M.owned[b]) {
             atomicAdd(&M.edelta[b][cidx(M, kp, jp, ip)], g1(S.w)[n]);
@@ -1332,6 +1343,7 @@ __global__ void __launch_bounds__(kBlock)
     double vx = S.vx[n], vy = S.vy[n], vz = S.vz[n];
     int ip = S.ip[n], jp = S.jp[n], kp = S.kp[n];
     sample_block_face<NDIM>(M, P, B, b, rng, x, y, z, vx, vy, vz, ip, jp, kp);
+    JB_INV_FACE(M, b, x, y, z, ip, jp, kp, n, S.id);
     S.x[n] = x; S.y[n] = y; S.z[n] = z;
     S.vx[n] = vx; S.vy[n] = vy; S.vz[n] = vz;
     S.ip[n] = ip; S.jp[n] = jp; S.kp[n] = kp;
@@ -1348,6 +1360,67 @@ __global__ void __launch_bounds__(kBlock)
   c = wave_sum(c);
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(&counters[CNT_UNFINISHED], c);
 }
+
+#ifdef JB_INVARIANTS
+// (checked build) SWARM: slots [first, last).  Every slot: a defined status; an active (resident) photon:
+// block in range, indices in the interior (check_index), position inside the block, w and e finite and
+// >= 0, t <= t_end.  Each value is range-checked before it indexes anything.  (check_index = 0 on entry to a
+// transport task: a photon that arrived from another rank carries the indices its sender last gave it, which
+// the tracking kernels recompute from the position, as the reference does after comms, transport.cpp:95-96.)
+__global__ void __launch_bounds__(kBlock)
+    k_inv_swarm(DevMesh M, DevSwarm S, long long first, long long last, double t_end, int check_index) {
+  for (long long n = first + (long long)blockIdx.x * blockDim.x + threadIdx.x; n < last;
+       n += (long long)gridDim.x * blockDim.x) {
+    const int st = S.status[n];
+    bool ok = inv::status_ok(st);
+    int b = -1, ip = 0, jp = 0, kp = 0;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (st == ST_ACTIVE) {
+      b = S.blk[n];
+      ip = S.ip[n]; jp = S.jp[n]; kp = S.kp[n];
+      x = S.x[n]; y = S.y[n]; z = S.z[n];
+      const int I[3] = {ip, jp, kp}, lo_i[3] = {M.is, M.js, M.ks}, hi_i[3] = {M.ie, M.je, M.ke};
+      ok = inv::block_ok(b, M.nblocks) && (!check_index || inv::index_ok(I, lo_i, hi_i)) &&
+           inv::attributes_ok(S.w[n], S.e[n], S.t[n], t_end);
+      if (inv::block_ok(b, M.nblocks)) {
+        const double X[3] = {x, y, z};
+        const double lo[3] = {M.blk_xmin[3 * b], M.blk_xmin[3 * b + 1], M.blk_xmin[3 * b + 2]};
+        const double hi[3] = {M.blk_xmax[3 * b], M.blk_xmax[3 * b + 1], M.blk_xmax[3 * b + 2]};
+        ok = ok && inv::position_ok(M.ndim, X, lo, hi);
+      }
+    }
+    inv::count_passes(JB_INV_FAM_SWARM, true);
+    inv::count(JB_INV_SWARM, true, ok);
+    if (!ok) inv::record_first(JB_INV_SWARM, JB_INV_FAM_SWARM, b, n, S.id, ip, jp, kp, x, y, z);
+  }
+}
+
+// (checked build) DDMC_CLASS, right after k_ddmc_pack: every interior cell whose code is a class number
+// (below max_classes) has that class's record bit for bit as its own step record
+__global__ void __launch_bounds__(kBlock) k_inv_ddmc_class(DevMesh M, int max_classes) {
+  const long long total = (long long)M.nblocks * M.ncell;
+  for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < total;
+       c += (long long)gridDim.x * blockDim.x) {
+    int b, k, j, i, cell;
+    decode_cell(M, c, b, k, j, i, cell);
+    const long long q = (long long)b * M.ntot + cidx(M, k, j, i);
+    const unsigned code = M.ddmc_code[q];
+    const bool evaluated = code < (unsigned)max_classes;
+    bool ok = true;
+    if (evaluated) {
+      uint64_t cls[8], own[8];
+      for (int w = 0; w < 8; ++w) {
+        cls[w] = (uint64_t)__double_as_longlong(M.ddmc_class[8 * (long long)code + w]);
+        own[w] = (uint64_t)__double_as_longlong(M.ddmc_step[8 * q + w]);
+      }
+      ok = inv::records_equal(cls, own);
+    }
+    inv::count_passes(JB_INV_FAM_DDMC_CLASS, true);
+    inv::count(JB_INV_DDMC_CLASS, evaluated, ok);
+    if (!ok) inv::record_first(JB_INV_DDMC_CLASS, JB_INV_FAM_DDMC_CLASS, b, -1, nullptr, i, j, k, 0.0, 0.0, 0.0);
+  }
+}
+#endif
 
 __global__ void __launch_bounds__(kBlock) k_zero_tally(DevMesh M) {
   const long long total = (long long)M.nblocks * M.ncell;

@@ -377,6 +377,28 @@ class MeshData:
         self._stats_cache = None
         return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
+    def invariants_enabled(self) -> bool:
+        """True under the checked library (libjaybenne_amd_checked.so, selected by JAYBENNE_AMD_LIB)."""
+        return self.lib.jb_invariants_enabled() == 1
+
+    def invariant_report(self, reset: bool = False) -> Dict[str, object]:
+        """The checked library's transport-invariant counts (jb_invariant_report_get): per kind evaluated and
+        violated, per kernel family the lane-passes checked, and the first violation (None when there is
+        none).  JaybenneError (JB_ERR_UNSUPPORTED) under the release library."""
+        r = _lib.InvariantReport()
+        _lib.check(self.lib.jb_invariant_report_get(self.pkg.ctx, C.byref(r), int(reset)))
+        return r.as_dict()
+
+    def verify_swarm(self, t_start: float, t_end: float) -> Dict[str, object]:
+        """The SWARM sweep over the live photons now (jb_verify_swarm); the counts of this sweep alone.
+        Does not raise on a violation: the caller reads the counts."""
+        r = _lib.InvariantReport()
+        st = self.lib.jb_verify_swarm(self.pkg.ctx, self.handle, C.byref(self.sv), float(t_start), float(t_end),
+                                      C.byref(r))
+        if st < 0 and st != _lib.JB_ERR_INVARIANT:
+            _lib.check(st)
+        return r.as_dict()
+
 
 # ------------------------------------------------------------------------------------------------
 # tasks (reference jaybenne.hpp:59-76)

@@ -18,7 +18,7 @@ from typing import Dict
 
 import numpy as np
 
-from . import constants
+from . import _lib, constants
 from .deck import ParameterInput
 from .mesh import Mesh
 
@@ -304,6 +304,18 @@ class McblockDriver:
 
     def Step(self):
         st = self.jb.RadiationStep(self.md, self.time, self.dt)
+        # (checked library, one rank) a step with new violations raises.  With several ranks the collective calls
+        # carry the verdict instead -- every rank gets JB_ERR_INVARIANT from the same call, so that no rank is
+        # left waiting in a collective for one that has stopped
+        if self.md.invariants_enabled() and self.md.nranks == 1:
+            seen = getattr(self, "_invariant_violations", 0)
+            rep = self.md.invariant_report()
+            total = sum(rep["violated"].values())
+            self._invariant_violations = total
+            if total > seen:
+                raise _lib.JaybenneError(_lib.JB_ERR_INVARIANT,
+                                         f"{total - seen} transport invariant violation(s) in cycle {self.ncycle}; "
+                                         f"first: {rep['first']}")
         if st != self.jb.TaskStatus.complete:
             return st
         self.HostUpdateTasks()
