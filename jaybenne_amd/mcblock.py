@@ -247,8 +247,11 @@ class McblockDriver:
 
     def __init__(self, pin: ParameterInput, rank: int = 0, nranks: int = 1, comm=None,
                  device=None, capacity_factor: float = 1.3, mesh: Mesh = None,
-                 halo_rings: int = 1, decomposition: str = "blocks"):
-        """``decomposition`` (several ranks): "blocks" -- the reference's: meshblocks dealt to ranks
+                 halo_rings: int = 1, decomposition: str = "blocks", initial_state=None):
+        """``initial_state``: a callable ``(mesh, pkg, gids=None) -> {"rho", "sie", "u"}`` with the shapes and
+        ghost conventions of ``ProblemGenerator``, used in its place (default: ``ProblemGenerator``).
+
+        ``decomposition`` (several ranks): "blocks" -- the reference's: meshblocks dealt to ranks
         (``Mesh.partition`` by the cost ``block_costs`` estimates), photons handed over where they
         leave a rank's blocks; "replicated" -- every rank holds the whole mesh and follows its share
         of every block's photons (``jaybenne.MeshData``: for meshes that fit every GPU many times
@@ -287,7 +290,7 @@ class McblockDriver:
         self.ncycle = 0
         self.dt = jb.EstimateTimestepMesh(self.md)
         # ProblemGenerator + PostInitialization + initial ghost fill / FillDerived
-        ic = ProblemGenerator(self.mesh, self.mcb, gids=self.md.resident_gids)
+        ic = (initial_state or ProblemGenerator)(self.mesh, self.mcb, gids=self.md.resident_gids)
         for name in ("rho", "sie", "u"):
             self.md.set_field(name, ic[name], local=True)
         jb.InitializeRadiation(self.md, self.mcb.initial_radiation == "thermal")

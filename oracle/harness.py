@@ -38,11 +38,13 @@ def oracle_params(pin: ParameterInput, pkg) -> dict:
 
 
 def make_oracle(pin: ParameterInput, math_mode: int, threads: int = 8, mesh: Mesh = None,
-                capacity_factor: float = 1.3):
+                capacity_factor: float = 1.3, initial_state=None):
+    """``initial_state``: as ``McblockDriver``'s -- a callable ``(mesh, pkg, gids=None)`` used in the place of
+    ``mcblock.ProblemGenerator``, so that both sides can start from one material state that is not the deck's."""
     from oracle import orc
     mesh = mesh if mesh is not None else Mesh.from_deck(pin)
     pkg = mcblock.Initialize(pin)
-    ic = mcblock.ProblemGenerator(mesh, pkg)
+    ic = (initial_state or mcblock.ProblemGenerator)(mesh, pkg)
     par = oracle_params(pin, pkg)
     O = orc.Oracle(mesh, par, capacity=int(par["num_particles"] * capacity_factor) + 4096,
                    math_mode=math_mode, threads=threads)

@@ -1,0 +1,361 @@
+"""Deterministic material states that differ from cell to cell, and the list of cases that run on them.
+
+Every parity deck has one density and (per side of the stepdiff step) one temperature, so a kernel that gathers
+a derived cell quantity from the wrong cell reads the right bits.  ``initial_state`` starts from
+``mcblock.ProblemGenerator``'s own output and multiplies rho (or sie) by a closed-form function of the PHYSICAL
+cell-centre position (or an integer hash of the global cell index): no RNG state, the same on every rank, the same
+for a block whatever its local index.  Ghost cells come from ``Mesh.fill_ghosts`` on the whole mesh.
+
+tests/test_hetero_host.py (CPU) checks that the states discriminate -- a one-cell shift changes the answer --,
+mix the regimes and produce the class counts the GPU cases rely on; tests/test_gpu_hetero.py runs the kernels on
+them.  Both import the case lists below.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from helpers import load_deck, make_oracle, run_oracle_cycles  # noqa: F401
+from jaybenne_amd import mcblock
+from test_gpu_parity import C5_LEVEL2, CASES as PARITY_CASES, SMR3D, SMR_OVERRIDES
+
+PATTERNS = ("smooth", "smooth_dense", "palette2", "palette3", "stripes3", "islands", "threshold", "hot_spots",
+            "hot_islands")
+PALETTES = {"palette2": (1.0, 1.5), "palette3": (1.0, 1.25, 1.5)}
+ISLAND_A = 2.0
+
+
+# ------------------------------------------------------------------------------------------------ geometry
+def cell_positions(mesh, b, shift=(0, 0, 0)):
+    """Cell-centre coordinates [nk, nj, ni] (ghost indices included) of block b, moved by ``shift`` cells of the
+    block's own width per axis; inactive axes sit at their single cell's centre."""
+    ax = [mesh.cell_centers(b, d) + (shift[d] * mesh.blk_dx[b, d] if d < mesh.ndim else 0.0) for d in range(3)]
+    Z, Y, X = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return X, Y, Z
+
+
+def global_cell_index(mesh, b, shift=(0, 0, 0)):
+    """Integer cell index of every cell of block b on the block's own level (ghosts: the index they would have)."""
+    ax = []
+    for d in range(3):
+        if d < mesh.ndim:
+            ax.append(int(mesh.blk_lloc[b, d]) * mesh.nx[d] + np.arange(mesh.ntot_dim[d]) - mesh.is_[d] + int(shift[d]))
+        else:
+            ax.append(np.zeros(mesh.ntot_dim[d], dtype=np.int64))
+    K, J, I = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return I.astype(np.int64), J.astype(np.int64), K.astype(np.int64)
+
+
+def _hash(i, j, k, level, salt):
+    m = np.uint64(0xffffffff)
+    h = (i.astype(np.uint64) * np.uint64(0x9E3779B1) + j.astype(np.uint64) * np.uint64(0x85EBCA77) +
+         k.astype(np.uint64) * np.uint64(0xC2B2AE3D) + np.uint64((int(level) * 0x27D4EB2F + int(salt) * 0x165667B1) & 0xffffffff)) & m
+    h ^= h >> np.uint64(15)
+    h = (h * np.uint64(0x2C1B3C6D)) & m
+    h ^= h >> np.uint64(12)
+    h = (h * np.uint64(0x297A2D39)) & m
+    h ^= h >> np.uint64(15)
+    return h
+
+
+def _smooth(X, Y, Z, ndim):
+    # unequal, coupled wave numbers: every cell different, no symmetry under axis exchange or reflection
+    f = np.sin(7.0 * X + 0.3)
+    if ndim >= 2:
+        f = f * np.cos(11.0 * Y - 0.2 + 3.0 * X)
+    if ndim >= 3:
+        f = f * np.cos(5.0 * Z + 1.1 + 2.0 * Y)
+    return f
+
+
+def _island_sign(X, Y, Z, ndim):
+    s = np.sin(23.0 * X + 2.0)
+    if ndim >= 2:
+        s = s + np.sin(29.0 * Y + 1.3 + 5.0 * X)
+    if ndim >= 3:
+        s = s + np.sin(19.0 * Z + 2.1 + 7.0 * Y)
+    return s > 0.0
+
+
+def _hot(X, Y, Z, ndim):
+    f = np.cos(9.0 * X - 0.7)
+    if ndim >= 2:
+        f = f * np.sin(13.0 * Y + 0.5 + 2.0 * X)
+    if ndim >= 3:
+        f = f * np.sin(6.0 * Z - 0.9 + 3.0 * Y)
+    return 1.0 + 0.5 * f
+
+
+def sigma_of(rho, pkg):
+    """ss + aa of a gray cell, operation for operation as the step loops form it."""
+    return (rho / pkg.scattering.apm) * pkg.scattering.kappa_s + rho * pkg.opacity.kappa
+
+
+def threshold_pair(dx_push, pkg, tau_ddmc):
+    """(rho_imc, rho_ddmc): neighbouring doubles with ``dx_push * sigma(rho_imc) > tau_ddmc`` false and the same for
+    rho_ddmc true -- found by stepping through the doubles until the oracle's own expression flips."""
+    per_rho = sigma_of(1.0, pkg)
+    rho = tau_ddmc / (dx_push * per_rho)
+    is_ddmc = lambda r: dx_push * sigma_of(r, pkg) > tau_ddmc   # noqa: E731
+    for _ in range(64):
+        if not is_ddmc(rho):
+            break
+        rho = np.nextafter(rho, 0.0)
+    for _ in range(64):
+        up = np.nextafter(rho, np.inf)
+        if is_ddmc(up):
+            assert not is_ddmc(rho)
+            return float(rho), float(up)
+        rho = up
+    raise AssertionError("no regime flip within 64 ulp of tau_ddmc / (dx sigma)")
+
+
+def rho_factor(mesh, pkg, pattern, b, shift=(0, 0, 0), salt=0, tau_ddmc=None):
+    """(factor on rho, factor on sie) of every cell of block b."""
+    X, Y, Z = cell_positions(mesh, b, shift)
+    one = np.ones_like(X)
+    nd = mesh.ndim
+    if pattern == "smooth":
+        return 1.0 + 0.5 * _smooth(X, Y, Z, nd), one
+    if pattern == "smooth_dense":
+        # in [1, 2]: stays on the DDMC side of every all-DDMC deck; shorter waves, because a DDMC history has a
+        # handful of events and a one-cell shift must still change it (test_hetero_host: discrimination)
+        f = np.sin(61.0 * X + 0.3)
+        if nd >= 2:
+            f = f * np.cos(47.0 * Y - 0.2 + 13.0 * X)
+        if nd >= 3:
+            f = f * np.cos(37.0 * Z + 1.1 + 17.0 * Y)
+        return 1.5 + 0.5 * f, one
+    if pattern == "stripes3":
+        # three densities dealt along skewed planes i + 2 j + 3 k: different in every axis, not symmetric under an
+        # exchange of axes, and -- unlike a hash, whose 3^(1 + 2 ndim) own-and-neighbour combinations overflow the
+        # class table in 3-D -- few distinct step records
+        pal = np.asarray(PALETTES["palette3"])
+        I, J, K = global_cell_index(mesh, b, shift)
+        return pal[((I + 2 * J + 3 * K + 5 * int(mesh.blk_level[b]) + int(salt)) // 2) % 3], one
+    if pattern in PALETTES:
+        pal = np.asarray(PALETTES[pattern])
+        I, J, K = global_cell_index(mesh, b, shift)
+        return pal[(_hash(I, J, K, mesh.blk_level[b], salt) % np.uint64(len(pal))).astype(np.int64)], one
+    if pattern in ("islands", "threshold", "hot_islands"):
+        f = np.where(_island_sign(X, Y, Z, nd), ISLAND_A, 1.0 / ISLAND_A)
+        if pattern == "threshold":
+            # every 5th cell (by hash) sits on the threshold itself: the largest density that is still IMC, or
+            # the next double, which is DDMC
+            I, J, K = global_cell_index(mesh, b, shift)
+            h = _hash(I, J, K, mesh.blk_level[b], 77 + salt)
+            lo, hi = threshold_pair(float(mesh.blk_dx[b, :nd].min()), pkg, tau_ddmc)
+            pick = (h % np.uint64(5)) == 0
+            val = np.where(((h >> np.uint64(8)) & np.uint64(1)) == 1, hi, lo) / pkg.initial_density
+            f = np.where(pick, val, f)
+        return f, (_hot(X, Y, Z, nd) if pattern == "hot_islands" else one)
+    if pattern == "hot_spots":
+        return one, _hot(X, Y, Z, nd)
+    raise ValueError(pattern)
+
+
+def initial_state(mesh, pkg, pattern, gids=None, shift=(0, 0, 0), salt=0, tau_ddmc=5.0):
+    """{"rho", "sie", "u"} as ``[len(gids), nk, nj, ni]`` with ghosts filled: ``mcblock.ProblemGenerator``'s state
+    times the pattern's factor."""
+    ic = mcblock.ProblemGenerator(mesh, pkg)
+    rho, sie = ic["rho"].copy(), ic["sie"].copy()
+    for b in range(mesh.nblocks):
+        fr, fs = rho_factor(mesh, pkg, pattern, b, shift, salt, tau_ddmc)
+        rho[b] *= fr
+        sie[b] *= fs
+    # (ghosts of rho and sie, then u = rho sie everywhere; ProblemGenerator exchanges rho and u instead -- under a
+    # coarse ghost with fine cells behind it the two differ by mean(rho) mean(sie) - mean(rho sie) where both
+    # vary.  Either is a legitimate state, and both sides of a comparison receive these same arrays)
+    mesh.fill_ghosts(rho)
+    mesh.fill_ghosts(sie)
+    u = rho * sie
+    out = {"rho": rho, "sie": sie, "u": u}
+    if gids is not None:
+        out = {k: np.ascontiguousarray(v[np.asarray(gids)]) for k, v in out.items()}
+    return out
+
+
+class State:
+    """Picklable ``initial_state=`` callable for ``McblockDriver`` and ``make_oracle`` (the worker processes of the
+    multi-rank cases receive it through spawn)."""
+
+    def __init__(self, pattern, shift=(0, 0, 0), salt=0, tau_ddmc=5.0):
+        self.pattern, self.shift, self.salt, self.tau_ddmc = pattern, tuple(shift), salt, tau_ddmc
+
+    def __call__(self, mesh, pkg, gids=None):
+        return initial_state(mesh, pkg, self.pattern, gids, self.shift, self.salt, self.tau_ddmc)
+
+
+def state_for(deck, overrides, pattern, shift=(0, 0, 0), salt=0):
+    pin = load_deck(deck, overrides)
+    return State(pattern, shift, salt, pin.GetOrAddReal("jaybenne", "tau_ddmc", 5.0))
+
+
+def oracle_on(deck, overrides, pattern, shift=(0, 0, 0), salt=0, threads=8, capacity_factor=1.3):
+    from oracle import orc
+    return make_oracle(load_deck(deck, overrides), orc.MATH_PORTABLE, threads=threads, capacity_factor=capacity_factor,
+                       initial_state=state_for(deck, overrides, pattern, shift, salt))
+
+
+# ------------------------------------------------------------------------------------------------ measurements
+def regime_map(mesh, pkg, rho, tau_ddmc):
+    """True where a cell takes DDMC steps: ``dx_push (ss + aa) > tau_ddmc`` (transport_ddmc.cpp:135), all cells."""
+    dx_push = mesh.blk_dx[:, :mesh.ndim].min(axis=1)[:, None, None, None]
+    return dx_push * sigma_of(rho, pkg) > tau_ddmc
+
+
+def step_records(mesh, pkg, O):
+    """The step record of every interior cell, [ncells, 8] -- {f sigma_a, sigma, six leak opacities P / dx} --
+    from the oracle's fleck, P1..P3 and rho, with the cell widths as the tracking loop forms them (upper face
+    minus lower face, faces from the cell centre: transport_ddmc.cpp:139-147)."""
+    m = mesh
+    sl = m.interior()
+    rho = O.fields["rho"]
+    rec = np.zeros(rho[sl].shape + (8,))
+    rec[..., 0] = O.fields["fleck"][sl] * (rho[sl] * pkg.opacity.kappa)
+    rec[..., 1] = rho[sl] * pkg.opacity.kappa + (rho[sl] / pkg.scattering.apm) * pkg.scattering.kappa_s
+    for d, name in enumerate(("P1", "P2", "P3")[:m.ndim]):
+        P = O.fields[name]
+        up = [slice(None)] + [slice(m.is_[dd] + (1 if dd == d else 0), m.is_[dd] + m.nx[dd] + (1 if dd == d else 0))
+                              for dd in (2, 1, 0)]
+        width = np.empty((m.nblocks, m.nx[d]))
+        for b in range(m.nblocks):
+            dx = m.blk_dx[b, d]
+            x0 = m.blk_xmin[b, d] - m.is_[d] * dx
+            xc = x0 + (np.arange(m.is_[d], m.is_[d] + m.nx[d]) + 0.5) * dx
+            width[b] = (xc + 0.5 * dx) - (xc - 0.5 * dx)
+        shape = [m.nblocks, 1, 1, 1]
+        shape[3 - d] = m.nx[d]
+        w = width.reshape(shape)
+        rec[..., 2 + 2 * d] = P[sl] / w
+        rec[..., 3 + 2 * d] = P[tuple(up)] / w
+    return rec.reshape(-1, 8)
+
+
+def class_count(mesh, pkg, O):
+    """Distinct step records of the mesh as k_ddmc_pack numbers them every cycle: what a DDMC step reads is
+    {f sigma_a, the running sums of the six leak opacities in face order} (DdmcStepRec; its eighth word is a
+    function of the others) -- sigma itself is not part of it, so two cells of different density whose sums with
+    their neighbours' agree share a class."""
+    o = step_records(mesh, pkg, O)
+    r = np.empty((len(o), 7))
+    r[:, 0] = o[:, 0]
+    r[:, 1] = o[:, 2]
+    r[:, 2] = o[:, 2] + o[:, 3]
+    for q in range(3, 7):
+        r[:, q] = r[:, q - 1] + o[:, q + 1]
+    r = np.ascontiguousarray(r)
+    return len(np.unique(r.view([("", r.dtype)] * 7)))
+
+
+def swarm_cells(mesh, sw, n):
+    return sw["blk"][:n].astype(np.int64), sw["kp"][:n].astype(np.int64), sw["jp"][:n].astype(np.int64), \
+        sw["ip"][:n].astype(np.int64)
+
+
+def regime_crossings(ddmc, before, after):
+    """(share of the photons that started in an IMC cell and ended in a DDMC one, and the reverse); ``before`` /
+    ``after``: (blk, kp, jp, ip) of the same photons in the same order."""
+    a, b = ddmc[before], ddmc[after]
+    return float(np.mean(~a & b)), float(np.mean(a & ~b))
+
+
+def differing_photons(A, B):
+    """Share of the photons of oracle run A (found by creation id) that are missing from run B or differ from
+    their twin there in any attribute."""
+    ia, ib = A.sw["id"][:A.n], B.sw["id"][:B.n]
+    oa, ob = np.argsort(ia), np.argsort(ib)
+    pos = np.searchsorted(ib[ob], ia[oa])
+    found = (pos < B.n) & (ib[ob][np.minimum(pos, B.n - 1)] == ia[oa])
+    diff = ~found
+    qa, qb = oa[found], ob[pos[found]]
+    for k in A.sw:
+        diff[found] |= A.sw[k][:A.n][qa] != B.sw[k][:B.n][qb]
+    return float(diff.mean())
+
+
+# ------------------------------------------------------------------------------------------------ cases
+def _mesh(**n):
+    """Mesh and block sizes as deck overrides: _mesh(nx=(16, 8, 8), bx=(8, 4, 4))."""
+    out = {}
+    for d, v in enumerate(n["nx"]):
+        out[f"parthenon/mesh/nx{d + 1}"] = v
+    for d, v in enumerate(n["bx"]):
+        out[f"parthenon/meshblock/nx{d + 1}"] = v
+    return out
+
+
+# (the meshes of test_gpu_parity.CASES, written out: a reordering there must not change them here)
+MESH_3D_8 = _mesh(nx=(16, 8, 8), bx=(8, 4, 4))            # 8 blocks
+MESH_3D_DDMC = dict(_mesh(nx=(128, 16, 16), bx=(32, 8, 8)), **{"jaybenne/tau_ddmc": 5.0})   # 16 blocks
+MESH_3D_ODD = _mesh(nx=(24, 12, 12), bx=(12, 6, 6))       # widths that are not powers of two
+MESH_2D_ODD = _mesh(nx=(120, 60), bx=(30, 30))            # ... on the hybrid deck
+for _m in (MESH_3D_8, MESH_3D_DDMC, MESH_3D_ODD, MESH_2D_ODD):
+    assert any(all(c[1].get(k) == v for k, v in _m.items()) for c in PARITY_CASES), _m
+
+SCAT = "mcblock/scattering_constant_value"
+
+# a / b: pure IMC.  (id, deck, overrides, pattern, kernel dimension); the scattering opacity is chosen so that a
+# mean free path is about a cell width: a history has collisions and face crossings
+IMC_CASES = [
+    ("imc-1d", "stepdiff", {"jaybenne/num_particles": 4000, SCAT: 150.0}, "smooth", 1),
+    ("imc-2d-smr", "stepdiff_smr", dict(SMR_OVERRIDES, **{"jaybenne/num_particles": 6000, SCAT: 100.0}), "smooth", 2),
+    ("imc-3d", "stepdiff", dict(MESH_3D_8, **{"jaybenne/num_particles": 3000, SCAT: 20.0}), "smooth", 3),
+    ("imc-3d-smr", "stepdiff_smr", dict(SMR3D, **{"jaybenne/num_particles": 20000, SCAT: 50.0}), "smooth", 3),
+    ("imc-3d-odd", "stepdiff", dict(MESH_3D_ODD, **{"jaybenne/num_particles": 4000, SCAT: 30.0}), "smooth", 3),
+]
+ABSORBING = {"mcblock/opacity_model": "constant", "mcblock/opacity_constant_value": 5.0,
+             "mcblock/initial_temperature": 1.0e6, "jaybenne/do_emission": "true", "jaybenne/do_feedback": "false"}
+IMC_HOT_CASE = ("imc-3d-hot", "stepdiff", dict(MESH_3D_8, **ABSORBING, **{"jaybenne/num_particles": 6000, SCAT: 20.0}),
+                "hot_spots", 3)
+
+# c: all-DDMC meshes (name, deck, overrides, ndim)
+DDMC_MESHES = [
+    ("1d", "stepdiff_ddmc", {"jaybenne/num_particles": 20000}, 1),
+    ("2d-smr", "stepdiff_smr_ddmc", dict(SMR_OVERRIDES, **{"jaybenne/num_particles": 30000}), 2),
+    ("3d", "stepdiff_ddmc", dict(MESH_3D_DDMC, **{"jaybenne/num_particles": 30000}), 3),
+    ("3d-smr", "stepdiff_smr_ddmc", dict(SMR3D, **{"jaybenne/num_particles": 30000}), 3),
+]
+# the palette each all-DDMC mesh runs the cell codes on: the one whose class count (test_hetero_host) fits the
+# class table of 256 records -- a cell's record depends on its own density and its 2 ndim neighbours'
+DDMC_PALETTE = {"1d": "palette3", "2d-smr": "palette2", "3d": "palette2", "3d-smr": "stripes3"}
+# ... and the bracket (lo, hi] its class count must fall into (launch_transport: at most 64 classes lets a small
+# mesh keep codes and records in LDS, at most 256 lets the codes be used at all): asserted in test_hetero_host
+DDMC_CLASS_BRACKET = {"1d": (0, 64), "2d-smr": (64, 256), "3d": (64, 256), "3d-smr": (64, 256)}
+DDMC_GATHERS = ["0", "1", "2", "default"]                     # on smooth_dense: the 64-byte forms
+DDMC_CODES = ["forced", "queues", "queues, codes gathered", "one class allowed", "no class allowed"]
+
+# e: hybrid meshes (name, deck, overrides, cycles)
+HYBRID_MESHES = [
+    ("2d", "stepdiff_smr_hybrid", {"jaybenne/num_particles": 30000}, 2),
+    ("2d-3lev", "stepdiff_smr_hybrid", dict(C5_LEVEL2, **{"jaybenne/num_particles": 30000}), 2),
+    ("3d-smr", "stepdiff_smr_hybrid", dict(SMR3D, **{"jaybenne/num_particles": 30000, "jaybenne/tau_ddmc": 20.0}), 1),
+    ("2d-odd", "stepdiff_smr_hybrid", dict(MESH_2D_ODD, **{"jaybenne/num_particles": 30000}), 1),
+]
+HYBRID_PATTERNS = ["islands", "threshold"]
+
+# f: feedback in 2-D
+FEEDBACK_CASE = ("stepdiff_smr_hybrid",
+                 {"jaybenne/num_particles": 30000, "mcblock/opacity_model": "constant",
+                  "mcblock/opacity_constant_value": 40.0, "mcblock/initial_temperature": 1.0e6,
+                  "jaybenne/do_emission": "true", "jaybenne/do_feedback": "true"}, "hot_islands", 3)
+
+# g: several ranks (id, deck, overrides, pattern, cycles)
+RANK_CASES = [
+    ("imc-2d-smr", IMC_CASES[1][1], IMC_CASES[1][2], "smooth", 1),
+    ("hybrid-2d", HYBRID_MESHES[0][1], HYBRID_MESHES[0][2], "islands", 1),
+    ("hybrid-2d-3lev", HYBRID_MESHES[1][1], HYBRID_MESHES[1][2], "islands", 1),
+    ("ddmc-3d-smr", DDMC_MESHES[3][1], DDMC_MESHES[3][2], "stripes3", 2),
+]
+
+
+def all_deck_patterns():
+    """Every (id, deck, overrides, pattern) the GPU file runs: what the CPU conditions are checked on."""
+    out = [(c[0], c[1], c[2], c[3]) for c in IMC_CASES + [IMC_HOT_CASE]]
+    for name, deck, ov, _ in DDMC_MESHES:
+        out.append((f"ddmc-{name}-smooth_dense", deck, ov, "smooth_dense"))
+        out.append((f"ddmc-{name}-{DDMC_PALETTE[name]}", deck, ov, DDMC_PALETTE[name]))
+    for name, deck, ov, _ in HYBRID_MESHES:
+        for pat in HYBRID_PATTERNS:
+            out.append((f"hybrid-{name}-{pat}", deck, ov, pat))
+    out.append(("feedback-2d", FEEDBACK_CASE[0], FEEDBACK_CASE[1], FEEDBACK_CASE[2]))
+    return out
