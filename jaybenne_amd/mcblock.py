@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib, constants
 from .deck import ParameterInput
-from .mesh import Mesh
+from .mesh import BC_PERIODIC, Mesh
 
 EOS_IDEAL_GAS = 0
 OPAC_GRAY = 0
@@ -145,9 +145,12 @@ def ProblemGenerator(mesh: Mesh, pkg: McblockPackage, gids=None,
     mcblock.cpp:155-203, 237-262 followed by the ghost exchange + FillDerived that Parthenon runs
     at the end of initialisation).
 
-    The stepdiff state is a function of x1 alone with its step on a block boundary, so the ghost
-    exchange has a closed form: evaluate the same function at the ghost-cell centre, clamped
-    into the domain in x1 (outflow copies the edge cell), periodic in x2/x3.
+    The stepdiff state is a function of x1 alone, so the ghost exchange has a closed form whatever
+    the boundaries of x2 / x3 are: evaluate the same function at the ghost-cell centre, moved into
+    the domain in x1 -- clamped where the mesh boundary is outflow (which copies the edge cell),
+    wrapped where it is periodic.  (The step must lie on a cell face of every level or, on a mesh of
+    one level, anywhere: a coarse ghost cell with fine cells on both sides of the step behind it
+    would hold their mean.)
     ``analytic_ghosts=False`` runs the general by-position exchange of ``Mesh.fill_ghosts``
     instead (whole mesh only); tests check that both agree."""
     cv = pkg.eos.SpecificHeatFromDensityInternalEnergy(pkg.initial_density, 1.0)
@@ -164,7 +167,15 @@ def ProblemGenerator(mesh: Mesh, pkg: McblockPackage, gids=None,
             x1v = mesh.cell_centers(int(b), 0)
             if analytic_ghosts:
                 half = 0.5 * mesh.blk_dx[int(b), 0]
-                x1v = np.clip(x1v, mesh.gmin[0] + half, mesh.gmax[0] - half)
+                ext = mesh.gmax[0] - mesh.gmin[0]
+                if mesh.mesh_bc[0] == BC_PERIODIC:
+                    x1v = np.where(x1v < mesh.gmin[0], x1v + ext, x1v)
+                else:
+                    x1v = np.maximum(x1v, mesh.gmin[0] + half)
+                if mesh.mesh_bc[1] == BC_PERIODIC:
+                    x1v = np.where(x1v > mesh.gmax[0], x1v - ext, x1v)
+                else:
+                    x1v = np.minimum(x1v, mesh.gmax[0] - half)
             sie[n][:, :, x1v >= 0.0] = cv * ttlow
     u = rho * sie                       # PostInitialization
     if not analytic_ghosts:
