@@ -385,6 +385,9 @@ int main(int argc, char **argv) {
       iterations_total += md->last_step.transport_iterations;
       handed_total += md->last_step.sent;
       compactions_total += md->last_step.capacity_rounds;
+      // JB_LEDGER=1: the cycle's energy ledger, reduced over the ranks inside the call (the same bits on every rank)
+      if (rank == 0 && jaybenne_amd::LedgerEnabled(md.get()))
+        std::printf("ledger %s\n", jaybenne_amd::LedgerJson(md->ledger).c_str());
     } else {
     JB_OK(jb_update_derived_transport_fields(ctx, mesh, p.dt));
     JB_OK(jb_zero_energy_tally(ctx, mesh));

@@ -2,7 +2,7 @@
 // what the reference's src/mcblock does around the jaybenne package, on one GPU, with no Python
 // and no PyTorch in the process.
 //
-//   mcblock_amd -i <deck> [block/key=value ...] [--tolerance X] [--dump file]
+//   mcblock_amd -i <deck> [block/key=value ...] [--tolerance X] [--dump file] [--ledger file]
 //
 // Input deck syntax and the trailing overrides are Parthenon's (reference inputs/*.in; the
 // regression harness tst/regression_test.py:85-145 rewrites decks the same way).  It sets up the
@@ -187,7 +187,7 @@ static uint64_t Morton(const int l[3], int bits) {
 
 int main(int argc, char **argv) {
   try {
-    std::string deck, dump;
+    std::string deck, dump, ledger_path;
     double tolerance = -1.0;
     std::vector<std::string> overrides;
     for (int a = 1; a < argc; ++a) {
@@ -195,10 +195,11 @@ int main(int argc, char **argv) {
       if (s == "-i" && a + 1 < argc) deck = argv[++a];
       else if (s == "--tolerance" && a + 1 < argc) tolerance = std::stod(argv[++a]);
       else if (s == "--dump" && a + 1 < argc) dump = argv[++a];
+      else if (s == "--ledger" && a + 1 < argc) ledger_path = argv[++a];
       else overrides.push_back(s);
     }
     if (deck.empty()) {
-      std::fprintf(stderr, "usage: mcblock_amd -i deck [block/key=value ...] [--tolerance X] [--dump file]\n");
+      std::fprintf(stderr, "usage: mcblock_amd -i deck [block/key=value ...] [--tolerance X] [--dump file] [--ledger file]\n");
       return 2;
     }
     ParameterInput pin;
@@ -577,6 +578,11 @@ int main(int argc, char **argv) {
     // (as the Python driver: the swarm sorted by block and cell after every k-th cycle; 0 = never)
     md.defrag_interval = (int)pin.GetOrAddInteger("jaybenne", "defrag_interval", -1);
     jb::InitializeRadiation(&md, initial_radiation == "thermal");
+    // --ledger FILE (or <jaybenne_amd> ledger = true, or JB_LEDGER=1): the energy ledger of every cycle
+    std::FILE *ledger_file = nullptr;
+    if (!ledger_path.empty() || pin.GetOrAddBoolean("jaybenne_amd", "ledger", false)) jb::EnableLedger(&md, true);
+    if (!ledger_path.empty() && !(ledger_file = std::fopen(ledger_path.c_str(), "w")))
+      throw std::runtime_error("cannot write " + ledger_path);
     std::printf("problem %s: %d-D, %d meshblocks, %d level(s), %lld photons\n", problem_id.c_str(), ndim,
                 nb, max_level + 1, (long long)md.swarm.n);
 
@@ -599,8 +605,29 @@ int main(int argc, char **argv) {
       }
       time += dt;
       ++ncycle;
-      std::printf("cycle=%ld time=%.6e dt=%.6e photons=%lld events=%lld\n", ncycle, time, dt,
+      std::printf("cycle=%ld time=%.6e dt=%.6e photons=%lld events=%lld", ncycle, time, dt,
                   (long long)md.swarm.n, (long long)md.events);
+      if (jb::LedgerEnabled(&md)) {
+        const jb::EnergyLedger &l = md.ledger;
+        if (ledger_file) std::fprintf(ledger_file, "%s\n", jb::LedgerJson(l).c_str());
+        std::printf(" leak=[%.6e, %.6e, %.6e, %.6e, %.6e, %.6e] residual=%.3e", l.e_escaped[0], l.e_escaped[1],
+                    l.e_escaped[2], l.e_escaped[3], l.e_escaped[4], l.e_escaped[5], l.residual);
+      }
+      std::printf("\n");
+    }
+    if (ledger_file) std::fclose(ledger_file);
+    if (jb::LedgerEnabled(&md)) {   // totals by face
+      static const char *const kFaces[6] = {"ix1", "ox1", "ix2", "ox2", "ix3", "ox3"};
+      std::printf("leakage by face:");
+      for (int f = 0; f < 6; ++f) {
+        double e = 0.0;
+        long long n = 0;
+        for (const auto &l : md.ledger_history) { e += l.e_escaped[f]; n += l.n_escaped[f]; }
+        std::printf(" %s=%.6e (%lld)", kFaces[f], e, n);
+      }
+      double worst = 0.0;
+      for (const auto &l : md.ledger_history) worst = l.residual > worst ? l.residual : worst;
+      std::printf("\nlargest residual=%.3e\n", worst);
     }
     HIP_OK(hipDeviceSynchronize());
 

@@ -142,7 +142,10 @@ typedef struct jb_swarm_view {
   int32_t *ip, *jp, *kp;  /* particle.photons.ijk[3] */
   int32_t *blk;           /* local block index (global id when status == JB_ST_OUTGOING) */
   int32_t *status;
-  uint64_t *id;
+  uint64_t *id;           /* creation index, below 2^63.  Of a slot that is NOT live -- the JB_ST_ABSORBED hole
+                             jb_unpack_incoming makes of an arrival that was absorbed on the sending rank -- the
+                             id carries bit 63: "deposited on behalf of another rank" (read by the energy
+                             ledger's sweep); holes vanish at the next jb_remove_marked_particles */
   uint64_t *rng;
 } jb_swarm_view;
 
@@ -508,6 +511,86 @@ typedef struct jb_step_report {
 jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, double t_start,
                                   double dt, uint64_t *next_id, uint32_t *cycle, int32_t *prefix_dev,
                                   const jb_rank_comm *comm, jb_step_report *report);
+
+/* ---- energy ledger -- how much energy went where in one radiation cycle, summed on the device (the
+ * reference has no such task: its hosts see counts only, and an escaped photon's weight vanishes when
+ * RemoveMarkedParticles closes its slot).  Off by default; with it off none of its kernels is launched and
+ * every call above behaves exactly as without it.  All terms are per cycle, for the blocks this rank owns.
+ * With E0 the e_census of the cycle before (of the initial swarm for the first: a jb_ledger_close before the
+ * first step returns it), summed over all ranks,
+ *     E0 + e_sourced = e_census + e_absorbed + sum_f e_escaped[f] + e_escaped_unclassified
+ * to rounding; the hosts print the residual relative to the left-hand side.
+ * The sums use no floating-point atomics (csrc/jb_kernel_ledger.hpp: registers -> LDS -> one line of partial
+ * sums per workgroup -> one workgroup that adds them in a fixed order): the same call on the same swarm gives
+ * the same bits.  Everything is enqueued on the context's stream; only jb_ledger_close synchronises (one
+ * copy of 184 bytes). */
+typedef struct jb_energy_ledger {
+  /* sum of w and number of the photons the emission source created this cycle (the slots SourcePhotons filled) */
+  double e_sourced; int64_t n_sourced;
+  /* ... of the photons that ended JB_ST_ESCAPED this cycle, by face (ix1, ox1, ix2, ox2, ix3, ox3): the first
+   * active axis d, in the order x1, x2, x3, on which the position left in the slot lies strictly outside --
+   * x_d < gmin[d]: face 2 d, x_d > gmax[d]: face 2 d + 1 -- the test on which the swarm boundaries let a
+   * photon go (boundaries.hpp:46-82 + Parthenon's outflow) */
+  double e_escaped[6]; int64_t n_escaped[6];
+  /* ... of the escaped photons for which that rule finds no outflow face.  Expected 0; never dropped. */
+  double e_escaped_unclassified; int64_t n_escaped_unclassified;
+  /* ... of the photons that ended JB_ST_ABSORBED or JB_ST_OUTGOING_ABSORBED in a transport call of this
+   * cycle, counted on the rank whose kernel absorbed them, before the hand-off turns packed slots into
+   * absorbed-looking holes (jb_pack_outgoing) */
+  double e_absorbed; int64_t n_absorbed;
+  /* ... of the JB_ST_ACTIVE photons when the cycle closes */
+  double e_census; int64_t n_census;
+  /* sum of energy_tally x cell volume over the interior cells of the owned blocks: agrees with e_census */
+  double e_tally;
+  /* sum of energy_delta over the same cells, raw.  energy_delta is an energy per cell, not a density
+   * (transport.cpp:159-161), and a reference quirk applies: the emission source OVERWRITES it with minus the
+   * emitted energy (sourcing.cpp:165-166,196) and without emission nothing ever resets it (SURVEY App. C
+   * quirk 5) -- with emission it is this cycle's absorbed minus emitted energy, without it the absorbed
+   * energy of all cycles so far */
+  double e_delta;
+  /* sum of HOST_UPDATE_ENERGY x cell volume over the same cells, after UpdateFluid */
+  double e_material;
+  double t_start, dt;
+  /* the cycle: *cycle of the step calls; jb_ledger_close called by a host returns 0 here and the host, which
+   * knows its cycle, sets it */
+  int64_t cycle;
+} jb_energy_ledger;
+enum { JB_LEDGER_SOURCED = 0, JB_LEDGER_TRANSPORTED = 1 };
+/* on != 0: allocates the ledger's buffers (once: 64 + 32 x 8 x CUs words, and 27 words per possible rank for
+ * jb_ledger_reduce) and zeroes the running sums.
+ * JB_LEDGER=1 in the environment makes on the default of jb_initialize, like JB_EXACT_ARITH.  Ranks that
+ * step together (jb_radiation_step_ranks) must all have it on or all off. */
+jb_status jb_ledger_enable(jb_context *ctx, int on);
+int jb_ledger_enabled(const jb_context *ctx);
+/* The task form, for a host that drives the tasks itself; adds to the running sums of the cycle.
+ *   JB_LEDGER_SOURCED: [first, last) = the slots jb_source_photons_fill has just filled (swarm->n updated).
+ *   JB_LEDGER_TRANSPORTED: [first, last) = the range a transport call has just followed; before any pack or
+ *     exchange, and with no slot in it that an earlier call in this cycle has counted.  The holes arrivals
+ *     absorbed on another rank become are told apart and skipped BY BIT 63 OF THEIR id, which
+ *     jb_unpack_incoming leaves there (see jb_swarm_view::id): a host that unpacks records with code of its
+ *     own must set that bit in such a hole's id too, or the absorption is counted on both ranks.
+ * Every escaped or absorbed photon is then counted exactly once, also when the swarm's holes are closed
+ * between two transport iterations.  JB_ERR_INVALID while the ledger is disabled. */
+jb_status jb_ledger_accumulate(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, int64_t first,
+                               int64_t last, int what);
+/* After UpdateFluid: sums the census ([0, swarm->n)) and the fields, reads the cycle's ledger back (the one
+ * synchronisation), zeroes the running sums.  out may be NULL (jb_ledger_last has it). */
+jb_status jb_ledger_close(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, double t_start,
+                          double dt, jb_energy_ledger *out);
+/* The ranks' ledgers through the transport's all_gather_u64 (doubles bit-cast), added in rank order: every
+ * rank ends with the same bits.  replicated != 0 (every rank holds every block and the all-reduced fields):
+ * swarm terms summed, field terms (e_tally, e_delta, e_material) taken once.  Collective.  nranks == 1:
+ * nothing to do (transport may be NULL).  The gather buffer is taken by jb_ledger_enable, so that nothing can
+ * fail on one rank alone before the collective.  Inside jb_radiation_step_ranks a rank whose close failed still
+ * makes the all-gather, with its status in front of its ledger, and every rank returns that failure. */
+jb_status jb_ledger_reduce(jb_context *ctx, const jb_exchange_transport *transport, int rank, int nranks,
+                           int replicated, jb_energy_ledger *inout);
+/* The ledger of the last completed jb_radiation_step / jb_radiation_step_ranks (reduced over the ranks:
+ * one more all-gather on every rank, inside the call) or jb_ledger_close.  With the ledger enabled the step
+ * calls do all of the above inside: the sourced sweep after the fill, a transported sweep after every transport
+ * launch over exactly the range it followed, before jb_exchange, the close after UpdateFluid.
+ * JB_ERR_INVALID while the ledger is disabled or before the first close. */
+jb_status jb_ledger_last(const jb_context *ctx, jb_energy_ledger *out);
 
 /* ---- transport invariants (checked library) -- the reference's PARTHENON_DEBUG_REQUIREs of the
  * tracking loop and of SampleDDMCBlockFace, evaluated on every pass (jaybenne_amd/csrc/jb_invariants.hpp).

@@ -19,6 +19,7 @@
 #define JAYBENNE_AMD_HPP_
 
 #include <cstdint>
+#include <cstdio>
 #include <cmath>
 #include <functional>
 #include <limits>
@@ -87,6 +88,23 @@ inline std::shared_ptr<StateDescriptor> Initialize(const jb_params &p, const jb_
   return std::make_shared<StateDescriptor>(p, opacity, scattering, eos, device);
 }
 
+// The energy ledger of one radiation cycle (jaybenne_amd.h: jb_energy_ledger), summed over the ranks, with the
+// census energy the cycle started from and the residual of
+//   e_start + e_sourced = e_census + e_absorbed + sum_f e_escaped[f] + e_escaped_unclassified
+// relative to its left-hand side.  LedgerResidual is a fixed sequence of IEEE operations, the one
+// jaybenne_amd/_lib.py: ledger_residual performs: both hosts print the same bits.
+struct EnergyLedger : jb_energy_ledger {
+  double e_start = 0.0, residual = 0.0;
+};
+inline double LedgerResidual(const jb_energy_ledger &l, double e_start) {
+  const double lhs = e_start + l.e_sourced;
+  double r = lhs - l.e_census;
+  r -= l.e_absorbed;
+  for (int f = 0; f < 6; ++f) r -= l.e_escaped[f];
+  r -= l.e_escaped_unclassified;
+  return lhs > 0.0 ? (r < 0.0 ? -r : r) / lhs : 0.0;
+}
+
 // The MeshData<Real> + swarm role: what one rank's tasks operate on.  The host fills `view`
 // (host arrays of per-block DEVICE pointers) and `swarm` (device arrays it allocated);
 // `reserve(n)` is the host's pool growth (Swarm::AddEmptyParticles, sourcing.cpp:123-131): it
@@ -134,6 +152,11 @@ class MeshData {
   int defrags = 0;
   int steps_since_defrag = 0;
   jb_step_report last_step{};   // what the last multi-rank RadiationStep did on this rank
+  // energy ledger (EnableLedger, or JB_LEDGER=1 in the environment): the last cycle's and every cycle's
+  EnergyLedger ledger{};
+  std::vector<EnergyLedger> ledger_history;
+  bool ledger_started = false;  // ledger_e0 holds the census energy the next cycle starts from
+  double ledger_e0 = 0.0;
 
  private:
   std::shared_ptr<StateDescriptor> pkg_;
@@ -552,13 +575,63 @@ inline void DefragAfterStep(MeshData *md, int64_t events) {
   }
 }
 
+// ---- energy ledger (jaybenne_amd.h: jb_ledger_*): off by default ----------------------------------
+inline bool LedgerEnabled(MeshData *md) { return jb_ledger_enabled(md->ctx()) == 1; }
+inline void EnableLedger(MeshData *md, bool on = true) {
+  Check(jb_ledger_enable(md->ctx(), on ? 1 : 0));
+  md->ledger = EnergyLedger{};
+  md->ledger_history.clear();
+  md->ledger_started = false;
+}
+// before the first cycle with the ledger on: the census energy it starts from (a close of its own; collective
+// when nranks > 1)
+inline void LedgerBegin(MeshData *md, const Real t_start, const jb_exchange_transport *tr = nullptr, int rank = 0,
+                        int nranks = 1) {
+  if (md->ledger_started) return;
+  jb_energy_ledger led{};
+  Check(jb_ledger_close(md->ctx(), md->mesh(), &md->swarm, t_start, 0.0, &led));
+  Check(jb_ledger_reduce(md->ctx(), tr, rank, nranks, 0, &led));
+  md->ledger_e0 = led.e_census;
+  md->ledger_started = true;
+}
+inline void LedgerRecord(MeshData *md, const jb_energy_ledger &led) {
+  EnergyLedger l{};
+  static_cast<jb_energy_ledger &>(l) = led;
+  l.e_start = md->ledger_e0;
+  l.residual = LedgerResidual(led, md->ledger_e0);
+  md->ledger_e0 = led.e_census;
+  md->ledger = l;
+  md->ledger_history.push_back(l);
+}
+// one cycle's ledger as a JSON line (the keys of `python -m jaybenne_amd --ledger`; %.17g restores the bits)
+inline std::string LedgerJson(const EnergyLedger &l) {
+  char buf[2048];
+  int n = std::snprintf(buf, sizeof buf, "{\"cycle\": %lld, \"t_start\": %.17g, \"dt\": %.17g, \"e_start\": %.17g, "
+                        "\"e_sourced\": %.17g, \"n_sourced\": %lld, \"e_escaped\": [%.17g, %.17g, %.17g, %.17g, %.17g, %.17g], "
+                        "\"n_escaped\": [%lld, %lld, %lld, %lld, %lld, %lld], \"e_escaped_unclassified\": %.17g, "
+                        "\"n_escaped_unclassified\": %lld, \"e_absorbed\": %.17g, \"n_absorbed\": %lld, \"e_census\": %.17g, "
+                        "\"n_census\": %lld, \"e_tally\": %.17g, \"e_delta\": %.17g, \"e_material\": %.17g, \"residual\": %.17g}",
+                        (long long)l.cycle, l.t_start, l.dt, l.e_start, l.e_sourced, (long long)l.n_sourced, l.e_escaped[0],
+                        l.e_escaped[1], l.e_escaped[2], l.e_escaped[3], l.e_escaped[4], l.e_escaped[5],
+                        (long long)l.n_escaped[0], (long long)l.n_escaped[1], (long long)l.n_escaped[2],
+                        (long long)l.n_escaped[3], (long long)l.n_escaped[4], (long long)l.n_escaped[5],
+                        l.e_escaped_unclassified, (long long)l.n_escaped_unclassified, l.e_absorbed, (long long)l.n_absorbed,
+                        l.e_census, (long long)l.n_census, l.e_tally, l.e_delta, l.e_material, l.residual);
+  return std::string(buf, n > 0 ? (size_t)n : 0);
+}
+
 // jaybenne::RadiationStep(pmesh, t_start, dt) for one rank -- jaybenne.cpp:68-151
 inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt) {
   TraceRange timestep("Jaybenne::Timestep");
   const jb_params &p = md->pkg().params();
+  const bool ledger = LedgerEnabled(md);
+  if (ledger) LedgerBegin(md, t_start);
   md->cycle += 1;
   UpdateDerivedTransportFields(md, dt);
+  const int64_t n_before = md->swarm.n;
   SourcePhotons(md, SourceType::emission, t_start, dt);
+  if (ledger && md->swarm.n > n_before)
+    Check(jb_ledger_accumulate(md->ctx(), md->mesh(), &md->swarm, n_before, md->swarm.n, JB_LEDGER_SOURCED));
   Check(jb_zero_energy_tally(md->ctx(), md->mesh()));
   jb_transport_stats before{}, after{};
   Check(jb_get_transport_stats(md->ctx(), &before, 0));
@@ -566,6 +639,8 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt)
     TraceRange loop("Jaybenne::TransportLoop");   // (one pass: every block crossing is resolved in flight)
     if (p.use_ddmc) TransportPhotons_DDMC(md, t_start, dt, /*fuse_census_tally=*/true);
     else TransportPhotons(md, t_start, dt, /*fuse_census_tally=*/true);
+    // (what this launch absorbed and let escape, before the compaction closes those slots)
+    if (ledger) Check(jb_ledger_accumulate(md->ctx(), md->mesh(), &md->swarm, 0, md->swarm.n, JB_LEDGER_TRANSPORTED));
   }
   Check(jb_get_transport_stats(md->ctx(), &after, 0));
   if (after.n_outgoing != before.n_outgoing)
@@ -575,6 +650,12 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt)
   md->events += after.n_events - before.n_events;
   if (CheckCompletion(md, t_start + dt) != TaskStatus::complete) return TaskStatus::iterate;
   UpdateFluid(md);
+  if (ledger) {
+    jb_energy_ledger led{};
+    Check(jb_ledger_close(md->ctx(), md->mesh(), &md->swarm, t_start, dt, &led));
+    led.cycle = (int64_t)md->cycle;
+    LedgerRecord(md, led);
+  }
   DefragAfterStep(md, after.n_events - before.n_events);
   return TaskStatus::complete;
 }
@@ -594,6 +675,8 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt,
   comm.transport = tr;
   comm.host = md;
   comm.reserve = &MeshData::ReserveTrampoline;
+  const bool ledger = LedgerEnabled(md);   // (on on every rank or on none: the step reduces it with one more all-gather)
+  if (ledger) LedgerBegin(md, t_start, tr, rank, nranks);
   uint32_t cycle = (uint32_t)md->cycle;
   jb_step_report rep{};
   const jb_status st = jb_radiation_step_ranks(md->ctx(), md->mesh(), &md->swarm, t_start, dt, &md->next_id, &cycle,
@@ -602,6 +685,11 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt,
   md->last_step = rep;
   if (Check(st) != TaskStatus::complete) return TaskStatus::iterate;
   md->events += rep.events;
+  if (ledger) {   // (closed and reduced over the ranks inside the call)
+    jb_energy_ledger led{};
+    Check(jb_ledger_last(md->ctx(), &led));
+    LedgerRecord(md, led);
+  }
   DefragAfterStep(md, rep.events);
   return TaskStatus::complete;
 }

@@ -19,6 +19,16 @@ import time
 import numpy as np
 
 
+def ledger_json(led: dict) -> str:
+    """One cycle's energy ledger as a JSON line (``--ledger FILE``; examples/mcblock_amd writes the same keys and
+    values): a float is written so that reading the line restores its bits."""
+    import json
+    keys = ("cycle", "t_start", "dt", "e_start", "e_sourced", "n_sourced", "e_escaped", "n_escaped",
+            "e_escaped_unclassified", "n_escaped_unclassified", "e_absorbed", "n_absorbed", "e_census", "n_census",
+            "e_tally", "e_delta", "e_material", "residual")
+    return json.dumps({k: led[k] for k in keys})
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m jaybenne_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -36,6 +46,9 @@ def main(argv=None) -> int:
                          "libhdf5) or .npz.  Without it a deck with a <parthenon/output0> block of "
                          "file_type = hdf5 writes <problem_id>.out0.final.phdf into --output-dir")
     ap.add_argument("--output-dir", default=None, help="directory for deck-driven dumps (default: none written)")
+    ap.add_argument("--ledger", default=None, metavar="FILE",
+                    help="switch the energy ledger on: one JSON line per cycle to FILE, leak by face and the "
+                         "residual of the energy balance on the per-cycle line, totals by face at the end")
     ap.add_argument("overrides", nargs="*", help="block/key=value")
     args = ap.parse_args(argv)
 
@@ -54,7 +67,8 @@ def main(argv=None) -> int:
     if not torch.cuda.is_available():
         print("jaybenne_amd needs a GPU (the history loop runs only as HIP kernels)", file=sys.stderr)
         return 2
-    drv = mcblock.McblockDriver(pin, device=torch.device("cuda", 0))
+    drv = mcblock.McblockDriver(pin, device=torch.device("cuda", 0), ledger=True if args.ledger else None)
+    ledger_file = open(args.ledger, "w") if args.ledger else None
     print(f"problem {drv.mcb.problem_id}: {drv.mesh.ndim}-D, {drv.mesh.nblocks} meshblocks, "
           f"levels {sorted(set(drv.mesh.blk_level.tolist()))}, {drv.md.n} photons")
     t0 = time.perf_counter()
@@ -67,8 +81,13 @@ def main(argv=None) -> int:
             drv.Step()
             torch.cuda.synchronize()
             dt = time.perf_counter() - c0
-            print(f"cycle={drv.ncycle} time={drv.time:.6e} dt={drv.dt:.6e} photons={drv.md.n} "
-                  f"histories/s={n0 / dt:.3e} events/s={(drv.md.events - e0) / dt:.3e}")
+            line = (f"cycle={drv.ncycle} time={drv.time:.6e} dt={drv.dt:.6e} photons={drv.md.n} "
+                    f"histories/s={n0 / dt:.3e} events/s={(drv.md.events - e0) / dt:.3e}")
+            if ledger_file is not None:
+                led = drv.md.ledger
+                ledger_file.write(ledger_json(led) + "\n")
+                line += " leak=[" + ", ".join(f"{e:.6e}" for e in led["e_escaped"]) + f"] residual={led['residual']:.3e}"
+            print(line)
     except JaybenneError as e:
         if not (checked and e.status == JB_ERR_INVARIANT):
             raise
@@ -76,6 +95,17 @@ def main(argv=None) -> int:
         print(f"TEST FAILED: {e}", file=sys.stderr)
         return 3
     print(f"walltime used = {time.perf_counter() - t0:.2f} s")
+    if ledger_file is not None:
+        ledger_file.close()
+        import math
+        from ._lib import LEDGER_FACES
+        hist = drv.md.ledger_history
+        print("leakage by face: " + " ".join(
+            f"{name}={math.fsum(h['e_escaped'][f] for h in hist):.6e} ({sum(h['n_escaped'][f] for h in hist)})"
+            for f, name in enumerate(LEDGER_FACES)))
+        print(f"sourced={math.fsum(h['e_sourced'] for h in hist):.6e} absorbed={math.fsum(h['e_absorbed'] for h in hist):.6e} "
+              f"unclassified={math.fsum(h['e_escaped_unclassified'] for h in hist):.6e} "
+              f"census={hist[-1]['e_census'] if hist else 0.0:.6e} largest residual={max((h['residual'] for h in hist), default=0.0):.3e}")
     if checked:
         print(f"invariants: {drv.md.invariant_report()}")
     tally = drv.md.get_field("tally")

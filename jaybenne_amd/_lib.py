@@ -141,6 +141,54 @@ class InvariantReport(C.Structure):
         return d
 
 
+# jb_energy_ledger (include/jaybenne_amd.h): where the energy of one radiation cycle went
+LEDGER_FACES = ("ix1", "ox1", "ix2", "ox2", "ix3", "ox3")
+JB_LEDGER_SOURCED, JB_LEDGER_TRANSPORTED = 0, 1
+
+
+class EnergyLedger(C.Structure):
+    _fields_ = [("e_sourced", C.c_double), ("n_sourced", C.c_int64),
+                ("e_escaped", C.c_double * 6), ("n_escaped", C.c_int64 * 6),
+                ("e_escaped_unclassified", C.c_double), ("n_escaped_unclassified", C.c_int64),
+                ("e_absorbed", C.c_double), ("n_absorbed", C.c_int64),
+                ("e_census", C.c_double), ("n_census", C.c_int64),
+                ("e_tally", C.c_double), ("e_delta", C.c_double), ("e_material", C.c_double),
+                ("t_start", C.c_double), ("dt", C.c_double), ("cycle", C.c_int64)]
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "EnergyLedger":
+        led = cls()
+        for name, kind in cls._fields_:
+            if name in ("e_escaped", "n_escaped"):
+                setattr(led, name, kind(*d[name]))
+            else:
+                setattr(led, name, d[name])
+        return led
+
+    def as_dict(self) -> dict:
+        d = {}
+        for name, kind in self._fields_:
+            v = getattr(self, name)
+            if name in ("e_escaped", "n_escaped"):
+                d[name] = [float(x) if kind._type_ is C.c_double else int(x) for x in v]
+            else:
+                d[name] = float(v) if kind is C.c_double else int(v)
+        return d
+
+
+def ledger_residual(led: dict, e_start: float) -> float:
+    """The residual of ``E0 + e_sourced = e_census + e_absorbed + sum_f e_escaped[f] + e_escaped_unclassified``
+    relative to its left-hand side (0.0 when that is zero): a fixed sequence of IEEE operations, the one
+    include/jaybenne_amd.hpp: LedgerResidual performs, so that every host prints the same bits."""
+    lhs = e_start + led["e_sourced"]
+    res = lhs - led["e_census"]
+    res -= led["e_absorbed"]
+    for e in led["e_escaped"]:
+        res -= e
+    res -= led["e_escaped_unclassified"]
+    return abs(res) / lhs if lhs > 0.0 else 0.0
+
+
 # every entry point include/jaybenne_amd.h declares: name -> (restype, argtypes)
 _vp, _i64, _f64, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
 PROTOTYPES = {
@@ -190,6 +238,12 @@ PROTOTYPES = {
                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _vp]),
     "jb_radiation_step_ranks": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint32), _vp, C.POINTER(RankComm), C.POINTER(StepReport)]),
+    "jb_ledger_enable": (_int, [_vp, _int]),
+    "jb_ledger_enabled": (_int, [_vp]),
+    "jb_ledger_accumulate": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, _i64, _int]),
+    "jb_ledger_close": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64, C.POINTER(EnergyLedger)]),
+    "jb_ledger_reduce": (_int, [_vp, C.POINTER(ExchangeTransport), _int, _int, _int, C.POINTER(EnergyLedger)]),
+    "jb_ledger_last": (_int, [_vp, C.POINTER(EnergyLedger)]),
     "jb_invariants_enabled": (_int, []),
     "jb_invariant_report_get": (_int, [_vp, C.POINTER(InvariantReport), _int]),
     "jb_verify_swarm": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64, C.POINTER(InvariantReport)]),

@@ -10,6 +10,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,6 +23,7 @@
 #include "jb_kernel_hybrid.hpp"
 #include "jb_kernel_ddmc_q.hpp"
 #include "jb_kernel_imc.hpp"
+#include "jb_kernel_ledger.hpp"
 
 using namespace jb;
 
@@ -99,7 +101,21 @@ struct jb_context {
   int min_interval = 2;              // cycles between two sorts (doubles when a sort bought nothing)
   int policy_sorts = 0;
   bool sort_scratch_tried = false;   // the sort's scratch records have been asked for (first policy call)
+  // energy ledger (jb_ledger_*; JB_LEDGER=1 at jb_initialize): off by default
+  bool ledger_on = false;
+  unsigned long long *ledger_d = nullptr;    // [kLedgerHead words: the running ledger | the workgroups' partial sums]
+  int ledger_parts = 0;                      // workgroups the partials have room for
+  unsigned long long *ledger_gather_d = nullptr;   // jb_ledger_reduce: this rank's ledger, then every rank's
+  size_t ledger_gather_words = 0;
+  jb_energy_ledger ledger_last{};
+  bool ledger_has_last = false;
 };
+constexpr int kLedgerHead = 64;   // words in front of the partial sums (LW_N of them used)
+constexpr int kLedgerWords = (int)(sizeof(jb_energy_ledger) / 8);
+constexpr int kLedgerGatherRow = kLedgerWords + 1;   // jb_ledger_reduce: [status | ledger] per rank
+static_assert(sizeof(jb_energy_ledger) == 26 * 8 && offsetof(jb_energy_ledger, e_material) == 8 * LW_E_MATERIAL &&
+              offsetof(jb_energy_ledger, n_escaped) == 8 * LW_N_ESCAPED && offsetof(jb_energy_ledger, e_census) == 8 * LW_E_CENSUS,
+              "the running ledger on the device is the head of jb_energy_ledger, word for word");
 constexpr int kTransportEventPairs = 64;
 constexpr int kRankEnd = 1024;                               // CNT_N.. | 16..17 cursors | 32..1023 per-rank counts
 constexpr int kCounterWords = kRankEnd + kQueues * kQueueStride;  // | 1024.. the queue heads, one line each (CNT_QUEUE)
@@ -403,6 +419,7 @@ extern "C" jb_status jb_initialize(const jb_params *params, const jb_eos *eos,
     const int v = atoi(e);
     ctx->max_classes = v < 0 ? 0 : (v > kMaxClasses ? kMaxClasses : v);
   }
+  const char *ledger_env = getenv("JB_LEDGER");
   ctx->dp.key0 = (uint32_t)params->seed;  // RngPool rng_pool(seed): unadjusted (quirk 1)
   ctx->dp.use_ddmc = params->use_ddmc;
   ctx->dp.do_feedback = params->do_feedback;
@@ -467,6 +484,13 @@ extern "C" jb_status jb_initialize(const jb_params *params, const jb_eos *eos,
     jb_finalize(ctx);
     return st;
   }
+  if (ledger_env && ledger_env[0] == '1') {
+    const jb_status lst = jb_ledger_enable(ctx, 1);
+    if (lst != JB_COMPLETE) {
+      jb_finalize(ctx);
+      return lst;
+    }
+  }
   *out = ctx;
   return JB_COMPLETE;
 }
@@ -481,6 +505,8 @@ extern "C" jb_status jb_finalize(jb_context *ctx) {
   if (ctx->step_send_d) (void)hipFree(ctx->step_send_d);
   if (ctx->step_recv_d) (void)hipFree(ctx->step_recv_d);
   if (ctx->step_gather_d) (void)hipFree(ctx->step_gather_d);
+  if (ctx->ledger_d) (void)hipFree(ctx->ledger_d);
+  if (ctx->ledger_gather_d) (void)hipFree(ctx->ledger_gather_d);
   for (hipEvent_t e : ctx->tev) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->sort_ev) if (e) (void)hipEventDestroy(e);
   delete ctx;
@@ -2131,6 +2157,179 @@ extern "C" jb_status jb_fill_cells(jb_context *ctx, jb_mesh *mesh, int field, in
 }
 
 // ------------------------------------------------------------------------------------------------
+// Energy ledger (jb_kernel_ledger.hpp): sweeps that write per-workgroup partial sums, one workgroup that adds
+// them in a fixed order into the running ledger on the device, one read-back when the cycle closes.
+extern "C" jb_status jb_ledger_enable(jb_context *ctx, int on) {
+  if (!ctx) return fail(JB_ERR_INVALID, "jb_ledger_enable: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  if (on && !ctx->ledger_d) {
+    const int parts = ctx->num_cu * 8;
+    JB_HIP(hipMalloc(&ctx->ledger_d, ((size_t)kLedgerHead + (size_t)parts * kLedgerStride) * sizeof(unsigned long long)));
+    ctx->ledger_parts = parts;
+  }
+  if (on && !ctx->ledger_gather_d) {
+    // (taken here, for any number of ranks the step call accepts: jb_ledger_reduce then has nothing left that
+    // can fail on one rank alone before its collective)
+    const size_t words = (size_t)kLedgerGatherRow * (size_t)(kRankEnd + 1);
+    JB_HIP(hipMalloc(&ctx->ledger_gather_d, words * sizeof(unsigned long long)));
+    ctx->ledger_gather_words = words;
+  }
+  if (on) JB_HIP(hipMemsetAsync(ctx->ledger_d, 0, kLedgerHead * sizeof(unsigned long long), ctx->stream));
+  ctx->ledger_on = on != 0;
+  ctx->ledger_has_last = false;
+  return JB_COMPLETE;
+}
+
+extern "C" int jb_ledger_enabled(const jb_context *ctx) { return ctx && ctx->ledger_on ? 1 : 0; }
+
+// one sweep over [first, last) and the sum of its partials, on the context's stream
+static jb_status ledger_sweep(jb_context *ctx, const DevMesh &M, const DevSwarm &S, long long first, long long last,
+                              int what) {
+  if (last <= first) return JB_COMPLETE;
+  // (a grid from the CU count, as grid_for; a workgroup takes kLedgerUnroll x kBlock slots per trip)
+  const long long tile = (long long)kLedgerUnroll * kBlock;
+  long long blocks = (last - first + tile - 1) / tile;
+  if (blocks > ctx->ledger_parts) blocks = ctx->ledger_parts;
+  unsigned long long *parts = ctx->ledger_d + kLedgerHead;
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  switch (what) {
+  case LEDGER_SOURCED: hipLaunchKernelGGL(k_ledger_sweep<LEDGER_SOURCED>, grid, block, 0, ctx->stream, M, S, first, last, parts); break;
+  case LEDGER_TRANSPORTED: hipLaunchKernelGGL(k_ledger_sweep<LEDGER_TRANSPORTED>, grid, block, 0, ctx->stream, M, S, first, last, parts); break;
+  default: hipLaunchKernelGGL(k_ledger_sweep<LEDGER_CENSUS>, grid, block, 0, ctx->stream, M, S, first, last, parts); break;
+  }
+  hipLaunchKernelGGL(k_ledger_final, dim3(1), block, 0, ctx->stream, (const unsigned long long *)parts, (int)blocks, what,
+                     ctx->ledger_d);
+  JB_HIP(hipGetLastError());
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_ledger_accumulate(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, int64_t first,
+                                          int64_t last, int what) {
+  if (!ctx || !mesh || !swarm) return fail(JB_ERR_INVALID, "jb_ledger_accumulate: null argument");
+  if (!ctx->ledger_on) return fail(JB_ERR_INVALID, "jb_ledger_accumulate: the energy ledger is disabled (jb_ledger_enable)");
+  if (what != JB_LEDGER_SOURCED && what != JB_LEDGER_TRANSPORTED)
+    return fail(JB_ERR_INVALID, "jb_ledger_accumulate: what = %d is neither JB_LEDGER_SOURCED nor JB_LEDGER_TRANSPORTED", what);
+  JB_HIP(hipSetDevice(ctx->device));
+  const jb_status st = check_swarm(swarm, "jb_ledger_accumulate");
+  if (st != JB_COMPLETE) return st;
+  if (first < 0 || last > swarm->n || first > last)
+    return fail(JB_ERR_INVALID, "jb_ledger_accumulate: particle range [%lld,%lld) outside the swarm (n = %lld)",
+                (long long)first, (long long)last, (long long)swarm->n);
+  return ledger_sweep(ctx, mesh->dm, dev_swarm(swarm), first, last,
+                      what == JB_LEDGER_SOURCED ? LEDGER_SOURCED : LEDGER_TRANSPORTED);
+}
+
+static jb_status ledger_close(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, double t_start, double dt,
+                              long long cycle, jb_energy_ledger *out) {
+  const DevMesh &M = mesh->dm;
+  jb_status st = ledger_sweep(ctx, M, dev_swarm(swarm), 0, swarm->n, LEDGER_CENSUS);
+  if (st != JB_COMPLETE) return st;
+  {
+    unsigned long long *parts = ctx->ledger_d + kLedgerHead;
+    int blocks = grid_for(ctx, (long long)M.nblocks * M.ncell);
+    if (blocks > ctx->ledger_parts) blocks = ctx->ledger_parts;
+    hipLaunchKernelGGL(k_ledger_fields, dim3(blocks), dim3(kBlock), 0, ctx->stream, M, parts);
+    hipLaunchKernelGGL(k_ledger_final, dim3(1), dim3(kBlock), 0, ctx->stream, (const unsigned long long *)parts, blocks,
+                       -1, ctx->ledger_d);
+    JB_HIP(hipGetLastError());
+  }
+  jb_energy_ledger led;
+  memset(&led, 0, sizeof led);
+  JB_HIP(hipMemcpyAsync(&led, ctx->ledger_d, LW_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipMemsetAsync(ctx->ledger_d, 0, kLedgerHead * sizeof(unsigned long long), ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  led.t_start = t_start;
+  led.dt = dt;
+  led.cycle = cycle;
+  ctx->ledger_last = led;
+  ctx->ledger_has_last = true;
+  if (out) *out = led;
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_ledger_close(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, double t_start,
+                                     double dt, jb_energy_ledger *out) {
+  if (!ctx || !mesh || !swarm) return fail(JB_ERR_INVALID, "jb_ledger_close: null argument");
+  if (!ctx->ledger_on) return fail(JB_ERR_INVALID, "jb_ledger_close: the energy ledger is disabled (jb_ledger_enable)");
+  JB_HIP(hipSetDevice(ctx->device));
+  const jb_status st = check_swarm(swarm, "jb_ledger_close");
+  if (st != JB_COMPLETE) return st;
+  return ledger_close(ctx, mesh, swarm, t_start, dt, 0, out);   // (cycle: the host's to set)
+}
+
+// The reduction with this rank's verdict on what led to it in front of its ledger: a rank whose close failed
+// still makes the collective, and every rank returns that failure (the lowest failing rank's) from the same call.
+static jb_status ledger_reduce(jb_context *ctx, const jb_exchange_transport *tr, int rank, int nranks, int replicated,
+                               jb_energy_ledger *inout, jb_status local) {
+  if (!ctx || !inout) return fail(JB_ERR_INVALID, "jb_ledger_reduce: null argument");
+  if (nranks < 1 || rank < 0 || rank >= nranks)
+    return fail(JB_ERR_INVALID, "jb_ledger_reduce: rank %d outside [0, nranks = %d)", rank, nranks);
+  if (nranks > 1 && (!tr || !tr->all_gather_u64))
+    return fail(JB_ERR_INVALID, "jb_ledger_reduce: %d ranks need a transport with all_gather_u64", nranks);
+  if (nranks == 1) return local;
+  JB_HIP(hipSetDevice(ctx->device));
+  const size_t words = (size_t)kLedgerGatherRow * (size_t)(nranks + 1);
+  if (ctx->ledger_gather_words < words) {
+    if (ctx->ledger_gather_d) (void)hipFree(ctx->ledger_gather_d);
+    ctx->ledger_gather_d = nullptr;
+    ctx->ledger_gather_words = 0;
+    JB_HIP(hipMalloc(&ctx->ledger_gather_d, words * sizeof(unsigned long long)));
+    ctx->ledger_gather_words = words;
+  }
+  unsigned long long *in_d = ctx->ledger_gather_d, *all_d = ctx->ledger_gather_d + kLedgerGatherRow;
+  std::vector<unsigned long long> mine((size_t)kLedgerGatherRow, 0), rows((size_t)kLedgerGatherRow * (size_t)nranks, 0);
+  mine[0] = local == JB_COMPLETE ? 0ull : (unsigned long long)(-(long long)local);
+  memcpy(&mine[1], inout, sizeof *inout);
+  JB_HIP(hipMemcpyAsync(in_d, mine.data(), mine.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+  if (tr->all_gather_u64(tr->handle, (const uint64_t *)in_d, (uint64_t *)all_d, kLedgerGatherRow, (void *)ctx->stream) != 0)
+    return fail(JB_ERR_HIP, "jb_ledger_reduce: the transport's all-gather failed");
+  JB_HIP(hipMemcpyAsync(rows.data(), all_d, rows.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  std::vector<jb_energy_ledger> all((size_t)nranks);
+  for (int q = 0; q < nranks; ++q) {
+    const unsigned long long w = rows[(size_t)q * kLedgerGatherRow];
+    if (w != 0) {
+      if (q == rank) return local;            // (jb_last_error: this rank's own reason)
+      return fail((jb_status)(-(long long)w), "jb_ledger_reduce: rank %d failed to close its ledger (status %d)", q,
+                  -(int)(long long)w);
+    }
+    memcpy(&all[(size_t)q], &rows[(size_t)q * kLedgerGatherRow + 1], sizeof(jb_energy_ledger));
+  }
+  // in rank order, from rank 0's: the same bits on every rank (cycle, t_start, dt are the same on all)
+  jb_energy_ledger sum = all[0];
+  for (int q = 1; q < nranks; ++q) {
+    const jb_energy_ledger &r = all[(size_t)q];
+    sum.e_sourced += r.e_sourced; sum.n_sourced += r.n_sourced;
+    for (int f = 0; f < 6; ++f) { sum.e_escaped[f] += r.e_escaped[f]; sum.n_escaped[f] += r.n_escaped[f]; }
+    sum.e_escaped_unclassified += r.e_escaped_unclassified; sum.n_escaped_unclassified += r.n_escaped_unclassified;
+    sum.e_absorbed += r.e_absorbed; sum.n_absorbed += r.n_absorbed;
+    sum.e_census += r.e_census; sum.n_census += r.n_census;
+    if (!replicated) {   // (replicated mesh: every rank holds the all-reduced fields; rank 0's stand for all)
+      sum.e_tally += r.e_tally; sum.e_delta += r.e_delta; sum.e_material += r.e_material;
+    }
+  }
+  *inout = sum;
+  if (ctx->ledger_on) {
+    ctx->ledger_last = sum;
+    ctx->ledger_has_last = true;
+  }
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_ledger_reduce(jb_context *ctx, const jb_exchange_transport *tr, int rank, int nranks,
+                                      int replicated, jb_energy_ledger *inout) {
+  return ledger_reduce(ctx, tr, rank, nranks, replicated, inout, JB_COMPLETE);
+}
+
+extern "C" jb_status jb_ledger_last(const jb_context *ctx, jb_energy_ledger *out) {
+  if (!ctx || !out) return fail(JB_ERR_INVALID, "jb_ledger_last: null argument");
+  if (!ctx->ledger_on) return fail(JB_ERR_INVALID, "jb_ledger_last: the energy ledger is disabled (jb_ledger_enable)");
+  if (!ctx->ledger_has_last) return fail(JB_ERR_INVALID, "jb_ledger_last: no cycle has been closed yet");
+  *out = ctx->ledger_last;
+  return JB_COMPLETE;
+}
+
+// ------------------------------------------------------------------------------------------------
 // RadiationStep for a mesh held entirely by this rank: the task list of jaybenne.cpp:104-138 with
 // the iterate-sublist collapsed to one launch (every block crossing is resolved in flight).
 static jb_status radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, double t_start, double dt,
@@ -2167,6 +2366,8 @@ static jb_status radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *s
     if (st != JB_COMPLETE) return st;
     swarm->n += tot;
     *next_id += (uint64_t)tot;
+    if (ctx->ledger_on && (st = ledger_sweep(ctx, M, dev_swarm(swarm), swarm->n - tot, swarm->n, LEDGER_SOURCED)) != JB_COMPLETE)
+      return st;
   }
   st = jb_zero_energy_tally(ctx, mesh);
   if (st != JB_COMPLETE) return st;
@@ -2178,6 +2379,9 @@ static jb_status radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *s
     st = transport_impl(ctx, mesh, swarm, t_start, dt, 0, swarm->n, 1, ctx->params.use_ddmc != 0);
   }
   if (st != JB_COMPLETE) return st;
+  // (energy ledger: what this launch absorbed and let escape, before the compaction closes those slots)
+  if (ctx->ledger_on && (st = ledger_sweep(ctx, M, dev_swarm(swarm), 0, swarm->n, LEDGER_TRANSPORTED)) != JB_COMPLETE)
+    return st;
   jb_transport_stats after;
   st = jb_get_transport_stats(ctx, &after, 0);
   if (st != JB_COMPLETE) return st;
@@ -2187,7 +2391,9 @@ static jb_status radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *s
     st = jb_remove_marked_particles(ctx, swarm);
     if (st != JB_COMPLETE) return st;
   }
-  return jb_update_fluid(ctx, mesh);
+  st = jb_update_fluid(ctx, mesh);
+  if (st != JB_COMPLETE || !ctx->ledger_on) return st;
+  return ledger_close(ctx, mesh, swarm, t_start, dt, (long long)*cycle, nullptr);
 }
 
 extern "C" jb_status jb_radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm,
@@ -2352,6 +2558,9 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
     if (st != JB_COMPLETE) return done(st);
     swarm->n += pl.total_local;
     *next_id = pl.next_id;
+    if (ctx->ledger_on &&
+        (st = ledger_sweep(ctx, M, dev_swarm(swarm), swarm->n - pl.total_local, swarm->n, LEDGER_SOURCED)) != JB_COMPLETE)
+      return done(st);
   }
   if ((st = jb_zero_energy_tally(ctx, mesh)) != JB_COMPLETE) return done(st);
   jb_transport_stats before;
@@ -2365,6 +2574,9 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
       const int64_t last = swarm->n;
       st = (ddmc ? jb_transport_photons_ddmc : jb_transport_photons)(ctx, mesh, swarm, t_start, dt, first, last, 1);
       if (st != JB_COMPLETE) return done(st);
+      // (energy ledger: exactly the range this launch followed, before the hand-off turns packed slots into holes)
+      if (ctx->ledger_on && (st = ledger_sweep(ctx, M, dev_swarm(swarm), first, last, LEDGER_TRANSPORTED)) != JB_COMPLETE)
+        return done(st);
       ++rep.transport_iterations;
       if (!multi) { finished = true; break; }   // (every block crossing was resolved in flight)
       int64_t nsent = 0, nrecv = 0, moved = 0, xf = first, xl = last;
@@ -2404,7 +2616,14 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
       after.n_outgoing != before.n_outgoing) {
     if ((st = jb_remove_marked_particles(ctx, swarm)) != JB_COMPLETE) return done(st);
   }
-  return done(jb_update_fluid(ctx, mesh));
+  st = jb_update_fluid(ctx, mesh);
+  if (st != JB_COMPLETE || !ctx->ledger_on) return done(st);
+  // the close, and one more all-gather made on every rank (the ledger is on on all of them or on none)
+  // (a rank whose close fails still makes it, with its verdict in front: every rank returns that failure)
+  jb_energy_ledger led;
+  memset(&led, 0, sizeof led);
+  st = ledger_close(ctx, mesh, swarm, t_start, dt, (long long)*cycle, &led);
+  return done(ledger_reduce(ctx, tr, rank, nranks, 0, &led, st));
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -93,7 +93,8 @@ struct DevParams {
 struct DevSwarm {
   double *x, *y, *z, *vx, *vy, *vz, *t, *w, *e;
   int *ip, *jp, *kp, *blk, *status;
-  uint64_t *id;   // creation index (diagnostic key, never read by the tracking kernel)
+  uint64_t *id;   // creation index (diagnostic key, never read by the tracking kernel); an ABSORBED hole that
+                  // k_unpack_incoming made of an arrival absorbed on its sender keeps bit 63 (jaybenne_amd.h)
   uint64_t *rng;  // LCG state of the particle's stream
 };
 

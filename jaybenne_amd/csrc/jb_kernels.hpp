@@ -1864,7 +1864,9 @@ __global__ void __launch_bounds__(kBlock)
     S.t[n] = __longlong_as_double(o[6]); S.w[n] = __longlong_as_double(o[7]);
     S.e[n] = __longlong_as_double(o[8]);
     const bool absorbed = ((unsigned long long)o[9] >> 63) != 0ull;
-    S.id[n] = (uint64_t)o[9] & ~(1ull << 63);
+    // (the hole an absorbed arrival becomes keeps bit 63 in its id: the energy ledger's sweep over the arrivals
+    // must not count a weight that the rank whose kernel absorbed it has counted, jb_kernel_ledger.hpp)
+    S.id[n] = absorbed ? (uint64_t)o[9] : ((uint64_t)o[9] & ~(1ull << 63));
     S.ip[n] = (int)(unsigned)(o[10] & 0xffffffffll);
     S.jp[n] = (int)(unsigned)((unsigned long long)o[10] >> 32);
     S.kp[n] = (int)(unsigned)(o[11] & 0xffffffffll);

@@ -250,6 +250,12 @@ class MeshData:
         self.defrag_interval = -1
         self.defrags = 0
         self._steps_since_defrag = 0
+        # energy ledger (include/jaybenne_amd.h: jb_energy_ledger; enable_ledger, or JB_LEDGER=1 in the environment):
+        # the last cycle's ledger as a dict, reduced over the ranks, and every cycle's
+        self.ledger: Optional[dict] = None
+        self.ledger_history: list = []
+        self._ledger_e0: Optional[float] = None     # e_census the next cycle starts from
+        self._ledger_handoff = None                 # a transport for jb_ledger_reduce where the hand-off has none
         self._make_mesh_handle(owner)
 
     def reserve(self, nslots: int) -> None:
@@ -343,6 +349,9 @@ class MeshData:
         if getattr(self, "_chandoff", None) is not None:
             self._chandoff.close()
             self._chandoff = None
+        if getattr(self, "_ledger_handoff", None) is not None:
+            self._ledger_handoff.close()
+            self._ledger_handoff = None
         if getattr(self, "handle", None) is not None:
             self.lib.jb_mesh_destroy(self.handle)
             self.handle = None
@@ -376,6 +385,55 @@ class MeshData:
         _lib.check(self.lib.jb_get_transport_stats(self.pkg.ctx, C.byref(st), int(reset)))
         self._stats_cache = None
         return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    # ---- energy ledger
+    def enable_ledger(self, on: bool = True) -> None:
+        """Switches the energy ledger of the library context on or off (``jb_ledger_enable``).  On: every
+        RadiationStep leaves ``md.ledger`` -- the terms of ``jb_energy_ledger`` summed over the ranks, plus
+        ``e_start`` (the census energy the cycle started from) and ``residual`` (of
+        ``e_start + e_sourced = e_census + e_absorbed + escaped``, relative to the left-hand side) -- and appends
+        it to ``md.ledger_history``."""
+        self._sync_stream()
+        _lib.check(self.lib.jb_ledger_enable(self.pkg.ctx, int(bool(on))))
+        self.ledger, self.ledger_history, self._ledger_e0 = None, [], None
+
+    def ledger_enabled(self) -> bool:
+        return self.lib.jb_ledger_enabled(self.pkg.ctx) == 1
+
+    def _ledger_transport(self):
+        """The jb_exchange_transport the ledgers of several ranks are gathered through."""
+        if self.nranks == 1:
+            return None
+        if self.handoff != "python":
+            self.ensure_handoff()
+            return C.byref(self._chandoff.tr)
+        if self._ledger_handoff is None:
+            from .handoff import CHandoff
+            self._ledger_handoff = CHandoff(self, "torch")
+        return C.byref(self._ledger_handoff.tr)
+
+    def _ledger_reduce(self, led: "_lib.EnergyLedger") -> None:
+        if self.nranks > 1:
+            self._sync_stream()
+            _lib.check(self.lib.jb_ledger_reduce(self.pkg.ctx, self._ledger_transport(), self.rank, self.nranks,
+                                                 int(self.replicated), C.byref(led)))
+
+    def _ledger_begin(self, t_start: float) -> None:
+        """Before the first cycle with the ledger on: the census energy it starts from (a close of its own)."""
+        if self._ledger_e0 is None:
+            led = _lib.EnergyLedger()
+            self._sync_stream()
+            _lib.check(self.lib.jb_ledger_close(self.pkg.ctx, self.handle, C.byref(self.sv), t_start, 0.0, C.byref(led)))
+            self._ledger_reduce(led)
+            self._ledger_e0 = float(led.e_census)
+
+    def _ledger_record(self, led: "_lib.EnergyLedger") -> None:
+        d = led.as_dict()
+        d["e_start"] = self._ledger_e0
+        d["residual"] = _lib.ledger_residual(d, self._ledger_e0)
+        self._ledger_e0 = d["e_census"]
+        self.ledger = d
+        self.ledger_history.append(d)
 
     def invariants_enabled(self) -> bool:
         """True under the checked library (libjaybenne_amd_checked.so, selected by JAYBENNE_AMD_LIB)."""
@@ -711,6 +769,9 @@ def _radiation_step_ranks(md: MeshData, t_start: float, dt: float) -> TaskStatus
         cb = _lib.RESERVE_FN(reserve)
         md._rank_comm = (_lib.RankComm(rank=md.rank, nranks=md.nranks, transport=transport, host=None, reserve=cb), cb)
     md._reserve_error = None
+    ledger = md.ledger_enabled()
+    if ledger:
+        md._ledger_begin(t_start)
     md._sync_stream()
     next_id, cycle, rep = C.c_uint64(md.next_id), C.c_uint32(md.cycle), _lib.StepReport()
     st = md.lib.jb_radiation_step_ranks(pkg.ctx, md.handle, C.byref(md.sv), t_start, dt, C.byref(next_id),
@@ -732,6 +793,10 @@ def _radiation_step_ranks(md: MeshData, t_start: float, dt: float) -> TaskStatus
     if st == _lib.JB_ITERATE:
         return TaskStatus.iterate
     md.events += int(rep.events)
+    if ledger:     # (closed and reduced over the ranks inside the call)
+        led = _lib.EnergyLedger()
+        _lib.check(md.lib.jb_ledger_last(pkg.ctx, C.byref(led)))
+        md._ledger_record(led)
     _defrag_after_step(md, int(rep.events))
     return TaskStatus.complete
 
@@ -742,10 +807,14 @@ def _transport_loop(md: MeshData, transport, use_ddmc: bool, t_start: float, dt:
     pkg = md.pkg
     first = 0
     md.transport_iterations = 0
+    ledger = md.ledger_enabled()
     for it in range(int(pkg.Param("max_transport_iterations"))):
         last = md.n
         with _Phase(md, f"transport[{min(it, 2)}]"):
             transport(md, t_start, dt, first, last, fuse_census_tally=True)
+            if ledger:   # exactly the range this launch followed, before the hand-off packs any of it
+                _lib.check(md.lib.jb_ledger_accumulate(pkg.ctx, md.handle, C.byref(md.sv), first, last,
+                                                       _lib.JB_LEDGER_TRANSPORTED))
         md.transport_iterations += 1
         md.transport_iterations_total += 1
         if (md.nranks == 1 or md.replicated) and not (md.force_exchange and md.comm is not None):
@@ -774,10 +843,17 @@ def _radiation_step(md: MeshData, t_start: float, dt: float) -> TaskStatus:
     pkg = md.pkg
     use_ddmc = bool(pkg.Param("use_ddmc"))
     transport = TransportPhotons_DDMC if use_ddmc else TransportPhotons
+    ledger = md.ledger_enabled()
+    if ledger:
+        md._ledger_begin(t_start)
     md.cycle += 1
     with _Phase(md, "derived+source"):
         UpdateDerivedTransportFields(md, dt)
+        n_before = md.n
         SourcePhotons(md, SourceType.emission, t_start, dt)
+        if ledger and md.n > n_before:
+            _lib.check(md.lib.jb_ledger_accumulate(pkg.ctx, md.handle, C.byref(md.sv), n_before, md.n,
+                                                   _lib.JB_LEDGER_SOURCED))
         if md.replicated and md.rank != 0 and not pkg.Param("do_emission"):
             # Replicated mesh without the emission source: nothing resets energy_delta (sourcing.cpp:41-43
             # returns before :165-166 -- SURVEY App. C quirk 5), so behind last cycle's all-reduce EVERY rank
@@ -807,6 +883,12 @@ def _radiation_step(md: MeshData, t_start: float, dt: float) -> TaskStatus:
             RemoveMarkedParticles(md)
         md.events += after["n_events"] - before["n_events"]
         UpdateFluid(md)
+        if ledger:
+            led = _lib.EnergyLedger()
+            _lib.check(md.lib.jb_ledger_close(pkg.ctx, md.handle, C.byref(md.sv), t_start, dt, C.byref(led)))
+            led.cycle = md.cycle
+            md._ledger_reduce(led)
+            md._ledger_record(led)
         _defrag_after_step(md, int(after["n_events"] - before["n_events"]))
     return TaskStatus.complete
 

@@ -258,9 +258,13 @@ class McblockDriver:
 
     def __init__(self, pin: ParameterInput, rank: int = 0, nranks: int = 1, comm=None,
                  device=None, capacity_factor: float = 1.3, mesh: Mesh = None,
-                 halo_rings: int = 1, decomposition: str = "blocks", initial_state=None):
+                 halo_rings: int = 1, decomposition: str = "blocks", initial_state=None, ledger=None):
         """``initial_state``: a callable ``(mesh, pkg, gids=None) -> {"rho", "sie", "u"}`` with the shapes and
         ghost conventions of ``ProblemGenerator``, used in its place (default: ``ProblemGenerator``).
+
+        ``ledger``: the energy ledger of every cycle (``md.ledger``, ``md.ledger_history``: sourced, absorbed,
+        census and escaped energy by boundary face, summed on the device -- include/jaybenne_amd.h,
+        ``jb_energy_ledger``).  Default: the deck's ``<jaybenne_amd> ledger`` (false), or on with JB_LEDGER=1.
 
         ``decomposition`` (several ranks): "blocks" -- the reference's: meshblocks dealt to ranks
         (``Mesh.partition`` by the cost ``block_costs`` estimates), photons handed over where they
@@ -295,6 +299,10 @@ class McblockDriver:
         # (not a parameter of the reference: DefragParticles -- here a sort of the swarm by cell, for
         # the locality of the cell gathers -- after every k-th cycle; 0 = never, as the reference)
         self.md.defrag_interval = pin.GetOrAddInteger("jaybenne", "defrag_interval", -1)
+        if ledger is None:
+            ledger = pin.GetOrAddBoolean("jaybenne_amd", "ledger", False) or self.md.ledger_enabled()
+        if bool(ledger) != self.md.ledger_enabled():
+            self.md.enable_ledger(bool(ledger))
         self.tlim = pin.GetReal("parthenon/time", "tlim")
         self.nlim = pin.GetOrAddInteger("parthenon/time", "nlim", -1)
         self.time = 0.0
