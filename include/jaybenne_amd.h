@@ -294,7 +294,8 @@ int jb_get_arithmetic(const jb_context *ctx);
  * through queues in LDS: k_ddmc_q, the default on such meshes; ", codes in LDS" behind that when the
  * mesh has at most 1024 cells and 64 distinct records and the codes sit in LDS too);
  * "k_hybrid<2, lean, exact geometry>" on a mesh that mixes IMC and DDMC cells (three launches: IMC
- * phase, DDMC phase, remainder); "" before the first launch.  jb_mesh_exact_geometry: 1 if every
+ * phase, DDMC phase, remainder); "" before the first launch.  The pointer is valid until the next
+ * transport call on this mesh or until the mesh is destroyed.  jb_mesh_exact_geometry: 1 if every
  * resident block has power-of-two cell widths and a lower corner that is a whole number of them
  * (and the per-cell arrays of the resident blocks span less than 4 GiB). */
 const char *jb_last_transport_variant(const jb_mesh *mesh);

@@ -24,6 +24,7 @@
 #include "jb_kernel_ddmc_q.hpp"
 #include "jb_kernel_imc.hpp"
 #include "jb_kernel_ledger.hpp"
+#include "jb_select.hpp"
 
 using namespace jb;
 
@@ -137,8 +138,7 @@ struct jb_mesh {
   // the cell-local kernels (k_imc_cell, k_hybrid MODE 3) step the photon's byte offset with 24-bit
   // multiply-adds of the BYTE strides 8 ni and 8 ni nj: both have to stay below 2^23
   bool cell_ok = false;
-  const char *last_variant = "";  // the k_transport instantiation launched last
-  const char *last_pair = "";     // ... and the k_ddmc_all launched beside it (gray DDMC), or ""
+  char last_variant[64] = "";  // variant_name of the last transport call's plan (jb_last_transport_variant)
   const DevMesh *dm_dev = nullptr;  // copy of dm in device memory (k_hybrid reads the view through it)
   const int *nbr_dq = nullptr;      // k_imc_cell: change of the cell's byte offset per (block, face) crossing
   bool uniform_geom = false;        // every resident block has the cell widths of block 0 (k_imc_cell<.., UNIFORM>)
@@ -1025,303 +1025,225 @@ extern "C" jb_status jb_source_photons_fill_range(jb_context *ctx, jb_mesh *mesh
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int NDIM, bool DDMC>
-static jb_status launch_transport(jb_context *ctx, jb_mesh *mesh, const DevSwarm &S, double t_start,
-                             double dt, long long first, long long last, bool tally) {
+// Transport.  WHICH tracking kernel a call runs is decided in one place, select_transport (jb_select.hpp);
+// what follows turns its plan into launches.
+
+// A runtime value as a template argument: f(std::integral_constant) for the one of the listed values that v has.
+template <int... Vs, class F>
+static void with_int(int v, F &&f) {
+  (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+template <class F>
+static void with_bool(bool v, F &&f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <auto Kernel>
+using kernel_c = std::integral_constant<decltype(Kernel), Kernel>;
+
+// The tracking kernels are persistent (waves draw particles from queues until they are empty), so the grid
+// is exactly what the chip holds at once: more workgroups would only start when the queues
+// are already drained.  JB_TRANSPORT_BLOCKS_PER_CU overrides the occupancy query (tuning aid).
+enum class Occupancy {
+  cached,           // one query per kernel instantiation and process (the kernels without dynamic LDS)
+  per_launch,       // the dynamic LDS -- tally and record table of a small mesh -- changes with the mesh: ask per launch
+  per_launch_cap3,  // ... and take at most 3 (TransportPlan::occ_cap3)
+  one_per_queue,    // no query: kQueues workgroups (the handful of photons k_ddmc_all hands over)
+};
+template <auto Kernel, class... Args>
+static void launch_persistent(jb_context *ctx, long long n, size_t dyn_lds, Occupancy policy, const Args &...args) {
+  int g = kQueues;
+  if (policy != Occupancy::one_per_queue) {
+    static int cached = 0;
+    int occ = policy == Occupancy::cached ? cached : 0;
+    if (occ < 1) {
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, Kernel, kBlock, dyn_lds) != hipSuccess || occ < 1) occ = 3;
+      if (policy == Occupancy::cached) cached = occ;
+    }
+    if (policy == Occupancy::per_launch_cap3 && occ > 3) occ = 3;
+    g = grid_for(ctx, n, ctx->blocks_per_cu_env > 0 ? ctx->blocks_per_cu_env : occ);
+  }
+  hipLaunchKernelGGL(Kernel, dim3(g), dim3(kBlock), dyn_lds, ctx->stream, args...);
+}
+
+// The dispatch functions below list the instantiations that exist, no others: every further one is a kernel
+// to compile.
+
+// k_transport<NDIM, DDMC, TALLY, GRAY, EXACT, LEAN>: EXACT and LEAN are variants of the gray IMC kernels
+template <int NDIM>
+static void launch_k_transport(jb_context *ctx, const jb_mesh *mesh, const TransportPlan &p, const DevSwarm &S,
+                               double t_start, double dt, long long first, long long last) {
+  with_bool(p.tally, [&](auto tc) {
+    with_int<0, 1, 2>(p.gray, [&](auto gc) {
+      constexpr bool T = decltype(tc)::value;
+      constexpr int G = decltype(gc)::value;
+      const auto go = [&](auto dc, auto xc, auto lc) {
+        launch_persistent<k_transport<NDIM, decltype(dc)::value, T, G, decltype(xc)::value, decltype(lc)::value>>(
+            ctx, last - first, 0, Occupancy::cached, mesh->dm, ctx->dp, S, t_start, dt, first, last,
+            ctx->counters_d, (const int *)nullptr);
+      };
+      if constexpr (G != 0) {
+        if (!p.ddmc) {
+          with_bool(p.exact, [&](auto xc) { with_bool(p.lean, [&](auto lc) { go(std::false_type{}, xc, lc); }); });
+          return;
+        }
+      }
+      with_bool(p.ddmc, [&](auto dc) { go(dc, std::false_type{}, std::false_type{}); });
+    });
+  });
+}
+
+// k_imc_cell<NDIM, TALLY, NOABS, UNIFORM>
+template <int NDIM>
+static void launch_k_imc_cell(jb_context *ctx, const jb_mesh *mesh, const TransportPlan &p, const DevSwarm &S,
+                              double t_start, double dt, long long first, long long last) {
+  with_bool(p.tally, [&](auto tc) {
+    with_bool(p.noabs, [&](auto nc) {
+      with_bool(p.uniform, [&](auto uc) {
+        launch_persistent<k_imc_cell<NDIM, decltype(tc)::value, decltype(nc)::value, decltype(uc)::value>>(
+            ctx, last - first, 0, Occupancy::cached, mesh->dm_dev, ctx->dp, S, t_start, dt, first, last,
+            ctx->counters_d, mesh->nbr_dq);
+      });
+    });
+  });
+}
+
+// k_hybrid<NDIM, TALLY, NOABS, MODE, PHASE> on entries [f, l) of list_in (nullptr: slots of the swarm), with the
+// queue heads cleared in front of it; PHASE 2 exists as <.., true, 0, 2> only (hybrid_phase)
+template <int NDIM>
+static void launch_k_hybrid(jb_context *ctx, const jb_mesh *mesh, const TransportPlan &p, int phase, Occupancy policy,
+                            const DevSwarm &S, double t_start, double dt, long long f, long long l,
+                            const unsigned *list_in, unsigned *list_out, unsigned long long *count_out,
+                            const unsigned long long *count_in) {
+  (void)hipMemsetAsync(ctx->counters_d + CNT_QUEUE, 0, kQueues * kQueueStride * sizeof(unsigned long long), ctx->stream);
+  const HybridPhase h = hybrid_phase(p, phase);
+  with_bool(p.tally, [&](auto tc) {
+    with_bool(h.noabs, [&](auto nc) {
+      with_int<0, 1, 2, 3>(h.mode, [&](auto mc) {
+        constexpr bool T = decltype(tc)::value, NA = decltype(nc)::value;
+        constexpr int MD = decltype(mc)::value;
+        const auto go = [&](auto kc) {
+          launch_persistent<decltype(kc)::value>(ctx, l - f, 0, policy, mesh->dm_dev, ctx->dp, S, t_start, dt, f, l,
+                                                 ctx->counters_d, list_in, list_out, count_out, count_in);
+        };
+        if constexpr (NA && MD == 0) {
+          if (phase == 2) return go(kernel_c<k_hybrid<NDIM, T, true, 0, 2>>{});
+        }
+        if (phase == 1) go(kernel_c<k_hybrid<NDIM, T, NA, MD, 1>>{});
+        else go(kernel_c<k_hybrid<NDIM, T, NA, MD, 0>>{});
+      });
+    });
+  });
+}
+
+// Every cell takes DDMC steps: k_ddmc_all<NDIM, TALLY, GATHER> or k_ddmc_q<NDIM, TALLY, LCODES>.
+// A particle that sits at a face of its cell when it is loaded or relocated (one in ~1e8) needs
+// the albedo step: the kernel lists it, and k_hybrid<.., both loops>, launched behind it on
+// that list (its length read on the device: no synchronisation), tracks it to the end.
+template <int NDIM>
+static jb_status launch_all_ddmc(jb_context *ctx, const jb_mesh *mesh, const TransportPlan &p, const DevSwarm &S,
+                                 double t_start, double dt, long long first, long long last) {
+  const jb_status st = ensure_scratch(ctx, (size_t)(last - first) / 2 + 16);
+  if (st != JB_COMPLETE) return st;
+  unsigned *handed = (unsigned *)ctx->scratch_d;
+  unsigned long long *n_handed = ctx->counters_d + kCursorBase;
+  (void)hipMemsetAsync(n_handed, 0, sizeof(unsigned long long), ctx->stream);
+  with_bool(p.tally, [&](auto tc) {
+    constexpr bool T = decltype(tc)::value;
+    const auto go = [&](auto kc) {
+      launch_persistent<decltype(kc)::value>(ctx, last - first, p.dyn_lds,
+                                             p.occ_cap3 ? Occupancy::per_launch_cap3 : Occupancy::per_launch,
+                                             mesh->dm_dev, ctx->dp, S, t_start, dt, first, last, ctx->counters_d,
+                                             (const int *)mesh->dm.not_all_ddmc, handed, n_handed);
+    };
+    if (p.family == Family::k_ddmc_q)
+      with_bool(p.lcodes, [&](auto lc) { go(kernel_c<k_ddmc_q<NDIM, T, decltype(lc)::value>>{}); });
+    else
+      with_int<0, 1, 2, 3, 4>(p.gather, [&](auto gc) { go(kernel_c<k_ddmc_all<NDIM, T, decltype(gc)::value>>{}); });
+  });
+  launch_k_hybrid<NDIM>(ctx, mesh, p, 0, Occupancy::one_per_queue, S, t_start, dt, 0ll, last - first, handed,
+                        nullptr, nullptr, n_handed);
+  return JB_COMPLETE;
+}
+
+// A mix of IMC and DDMC cells: the three launches of k_hybrid (select_transport says why three).  The lists of
+// parked photons (slot numbers, 4 bytes each) live in the context's scratch buffer.
+template <int NDIM>
+static jb_status launch_mixed(jb_context *ctx, const jb_mesh *mesh, const TransportPlan &p, const DevSwarm &S,
+                              double t_start, double dt, long long first, long long last) {
+  const long long nrange = last - first;
+  const jb_status st = ensure_scratch(ctx, (size_t)nrange + 16);  // 2 lists x 4 bytes x n
+  if (st != JB_COMPLETE) return st;
+  unsigned *list_d = (unsigned *)ctx->scratch_d;          // parked by phase 1, read by phase 2
+  unsigned *list_i = list_d + nrange;                     // parked by phase 2, read by phase 0
+  unsigned long long *cnt = ctx->counters_d + kCursorBase;  // [0] |list_d|, [1] |list_i|
+  volatile unsigned long long *cnt_h = ctx->counters_h + kCursorBase;
+  const auto launch = [&](int phase, long long f, long long l, const unsigned *lin, unsigned *lout,
+                          unsigned long long *cout) {
+    launch_k_hybrid<NDIM>(ctx, mesh, p, phase, Occupancy::cached, S, t_start, dt, f, l, lin, lout, cout, nullptr);
+  };
+  (void)hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), ctx->stream);
+  launch(1, first, last, nullptr, list_d, cnt);
+  (void)hipMemcpyAsync((void *)cnt_h, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  const long long n_d = (long long)cnt_h[0];
+  if (n_d == 0) return JB_COMPLETE;
+  launch(2, 0, n_d, list_d, list_i, cnt + 1);
+  (void)hipMemcpyAsync((void *)(cnt_h + 1), cnt + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  const long long n_i = (long long)cnt_h[1];
+  if (n_i == 0) return JB_COMPLETE;
+  launch(0, 0, n_i, list_i, nullptr, nullptr);
+  return JB_COMPLETE;
+}
+
+template <int NDIM>
+static jb_status launch_transport(jb_context *ctx, jb_mesh *mesh, const DevSwarm &S, double t_start, double dt,
+                                  long long first, long long last, bool tally, bool ddmc) {
   const DevMesh &M = mesh->dm;
-  // The kernel is persistent (waves draw particles from queues until they are empty), so the grid
-  // is exactly what the chip holds at once: more workgroups would only start when the queues
-  // are already drained.  JB_TRANSPORT_BLOCKS_PER_CU overrides the occupancy query (tuning aid).
-  const int per_cu_env = ctx->blocks_per_cu_env;
   const bool gray = M.lam_abs != nullptr;
   (void)hipMemsetAsync(ctx->counters_d + CNT_QUEUE, 0, kQueues * kQueueStride * sizeof(unsigned long long), ctx->stream);
-#define JB_LAUNCH_X(T, G, X, L)                                                                    \
-  do {                                                                                             \
-    static int occ = 0;  /* (one query per kernel instantiation and process) */                    \
-    if (occ < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(                                  \
-                        &occ, k_transport<NDIM, DDMC, T, G, X, L>, kBlock, 0) != hipSuccess || occ < 1)) \
-      occ = 3;                                                                                     \
-    const int g = grid_for(ctx, last - first, per_cu_env > 0 ? per_cu_env : occ);                  \
-    const int *pair_flag = nullptr;                                                                \
-    hipLaunchKernelGGL((k_transport<NDIM, DDMC, T, G, X, L>), dim3(g), dim3(kBlock), 0,            \
-                       ctx->stream, M, ctx->dp, S, t_start, dt, first, last, ctx->counters_d,      \
-                       pair_flag);                                                                 \
-    mesh->last_variant = NDIM == 1 ? "k_transport<1, " #T ", " #G ", " #X ", " #L ">"              \
-                         : NDIM == 2 ? "k_transport<2, " #T ", " #G ", " #X ", " #L ">"            \
-                                     : "k_transport<3, " #T ", " #G ", " #X ", " #L ">";           \
-  } while (0)
-  // (variant string: NDIM, TALLY, GRAY, EXACT geometry, LEAN arithmetic; the DDMC flag is the
-  // entry point that was called)
-  // lean arithmetic on exact geometry: the step in cell-local coordinates (jb_kernel_imc.hpp)
-  static const char *const imc_cell_names[3][2][2] = {
-      {{"k_imc_cell<1, false, false, lean>", "k_imc_cell<1, false, true, lean>"},
-       {"k_imc_cell<1, true, false, lean>", "k_imc_cell<1, true, true, lean>"}},
-      {{"k_imc_cell<2, false, false, lean>", "k_imc_cell<2, false, true, lean>"},
-       {"k_imc_cell<2, true, false, lean>", "k_imc_cell<2, true, true, lean>"}},
-      {{"k_imc_cell<3, false, false, lean>", "k_imc_cell<3, false, true, lean>"},
-       {"k_imc_cell<3, true, false, lean>", "k_imc_cell<3, true, true, lean>"}}};
-  (void)imc_cell_names;
-#define JB_LAUNCH_CELL_U(T, NA, U)                                                                 \
-  do {                                                                                             \
-    static int occ = 0;                                                                            \
-    if (occ < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(                                  \
-                        &occ, k_imc_cell<NDIM, T, NA, U>, kBlock, 0) != hipSuccess || occ < 1))    \
-      occ = 3;                                                                                     \
-    const int g = grid_for(ctx, last - first, per_cu_env > 0 ? per_cu_env : occ);                  \
-    hipLaunchKernelGGL((k_imc_cell<NDIM, T, NA, U>), dim3(g), dim3(kBlock), 0, ctx->stream, mesh->dm_dev, \
-                       ctx->dp, S, t_start, dt, first, last, ctx->counters_d, mesh->nbr_dq);       \
-    /* (variant string: NDIM, TALLY, NOABS, and the arithmetic) */                                 \
-    mesh->last_variant = imc_cell_names[NDIM - 1][(T) ? 1 : 0][(NA) ? 1 : 0];                      \
-  } while (0)
-#define JB_LAUNCH_CELL(T, NA)                                                                      \
-  do {                                                                                             \
-    if (mesh->uniform_geom) JB_LAUNCH_CELL_U(T, NA, true);                                         \
-    else JB_LAUNCH_CELL_U(T, NA, false);                                                           \
-  } while (0)
-#define JB_LAUNCH(T, G)                                                                            \
-  do {                                                                                             \
-    if constexpr (!DDMC && G != 0) {                                                               \
-      if (mesh->exact_geom) {                                                                      \
-        if (ctx->lean_arith && !ctx->no_imc_cell && mesh->cell_ok) JB_LAUNCH_CELL(T, (G == 2));    \
-        else if (ctx->lean_arith) JB_LAUNCH_X(T, G, true, true);                                   \
-        else JB_LAUNCH_X(T, G, true, false);                                                       \
-      } else {                                                                                     \
-        /* (the cell-local step does not care what the cell widths are: only its conversions to and \
-           from the swarm's coordinates round, by an ulp of the position) */                       \
-        if (ctx->lean_arith && !ctx->no_imc_cell && mesh->cell_ok) JB_LAUNCH_CELL(T, (G == 2));    \
-        else if (ctx->lean_arith) JB_LAUNCH_X(T, G, false, true);                                  \
-        else JB_LAUNCH_X(T, G, false, false);                                                      \
-      }                                                                                            \
-    } else {                                                                                       \
-      JB_LAUNCH_X(T, G, false, false);                                                             \
-    }                                                                                              \
-  } while (0)
-  mesh->last_pair = "";
-  if constexpr (DDMC) {
-    // Gray opacities: UpdateDerivedTransportFields has packed the cell records and left a flag on
-    // the device saying whether every cell takes DDMC steps.  Every cell: k_ddmc_all; a mix of IMC
-    // and DDMC cells: k_hybrid.  Both keep the per-block tables in LDS, so meshes with more resident
-    // blocks than fit there stay with the general kernel below.
-    if (gray && M.ddmc_cell && M.nblocks <= kLdsBlocks) {
-      if (mesh->not_all_ddmc_host < 0) {
-        int *flag_h = (int *)(ctx->counters_h + kCounterWords - 1);
-        flag_h[0] = 1; flag_h[1] = 0;
-        (void)hipMemcpyAsync(flag_h, M.not_all_ddmc, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-        JB_HIP(hipStreamSynchronize(ctx->stream));
-        mesh->not_all_ddmc_host = flag_h[0] != 0 ? 1 : 0;
-        mesh->nclass_host = flag_h[1];
-      }
-      const bool noabs_h = ctx->dp.kappa_a == 0.0;
-      if (mesh->not_all_ddmc_host == 0) {
-        // The quad-cooperative gather (jb_kernel_ddmc.hpp) addresses the step records with 32-bit byte
-        // offsets; it pays once the records no longer sit in the CU's vector L1 (measured, ms per
-        // 1e8 histories: 128^3 cells 31.5 -> 27.9, 64^3 7.2 -> 6.9, 32^3 equal, 128 cells in 1-D
-        // 11.6 -> 13.1: there every lookup hits L1 and the detour through LDS only adds latency).
-        const unsigned long long rec_bytes = 64ull * (unsigned long long)M.ntot * (unsigned long long)M.nblocks;
-        // (record numbers are 32-bit: fewer than 2^32 resident cells; 64-bit addresses when the records
-        // span 4 GiB or more -- JB_COOP_GATHER=2 forces that form on any table, for the parity tests)
-        const bool coop = rec_bytes < (64ull << 32) &&
-                          (ctx->coop_gather >= 0 ? ctx->coop_gather >= 1 : rec_bytes >= (1ull << 20));
-        const bool wide = coop && (rec_bytes >= (1ull << 32) || ctx->coop_gather == 2);
-        // ... and a mesh of at most kLdsRecCells cells (the reference's 1-D decks) keeps its records in
-        // LDS: 12.3 -> 10.3 ms per 1e8 histories on BASELINE configs[2] as shipped
-        const bool in_lds = !coop && ctx->coop_gather < 0 && (long long)M.nblocks * M.ntot <= (long long)kLdsRecCells;
-        // ... and everything between with at most kMaxClasses DISTINCT step records (k_ddmc_pack counts them
-        // every cycle: the gray decks have a handful) gathers a 4-byte cell code per step, the records in LDS
-        // (JB_COOP_GATHER=4 also on the smallest meshes; 0 / 1 / 2 keep the 64-byte forms, for tests and A/B)
-        const bool codes_ok = M.ddmc_code != nullptr && mesh->nclass_host >= 1 && mesh->nclass_host <= ctx->max_classes;
-        // ... and, with the codes, the wave's photons staged through queues in LDS (k_ddmc_q, jb_kernel_ddmc_q.hpp:
-        // the event loop at full width, the service phase in whole batches) -- any mesh size, up to kQBlocks
-        // resident blocks and 2^32 slots; JB_DDMC_QUEUES=0 keeps k_ddmc_all
-        const bool queues = codes_ok && ctx->ddmc_queues && ctx->coop_gather < 0 && M.nblocks <= kQBlocks &&
-                            last <= (1ll << 32);
-        const bool codes = queues || (codes_ok && (ctx->coop_gather == 4 || (ctx->coop_gather < 0 && !in_lds)));
-        const int gather = codes ? 4 : (coop ? (wide ? 3 : 1) : (in_lds ? 2 : 0));
-        // ... the codes themselves in LDS on a mesh of at most kLdsCodeCells cells (JB_DDMC_LDS_CODES=0: not)
-        // (and at most 64 classes: tally 8 KB + classes 4 KB + codes 4 KB + 37.7 KB static stay under the 64 KB a
-        // workgroup may have; with up to kMaxClasses = 256 records, 16 KB, the codes would not fit beside them)
-        const bool lcodes = queues && ctx->ddmc_lds_codes && (long long)M.nblocks * M.ntot <= (long long)kLdsCodeCells &&
-                            mesh->nclass_host <= 64;
-        // A particle that sits at a face of its cell when it is loaded or relocated (one in ~1e8) needs
-        // the albedo step: k_ddmc_all lists it, and k_hybrid<.., both loops>, launched behind it on
-        // that list (its length read on the device: no synchronisation), tracks it to the end.
-        {
-          const jb_status st_s = ensure_scratch(ctx, (size_t)(last - first) / 2 + 16);
-          if (st_s != JB_COMPLETE) return st_s;
-        }
-        unsigned *handed = (unsigned *)ctx->scratch_d;
-        unsigned long long *n_handed = ctx->counters_d + kCursorBase;
-        // (dynamic shared memory: the tally of a mesh with <= kLdsTally cells, resident blocks' ghosts included)
-        const size_t ncell_all = (size_t)M.nblocks * (size_t)M.ntot;
-        const size_t lds_tally_bytes =
-            (tally && (long long)ncell_all <= (long long)kLdsTally ? sizeof(double) * ((ncell_all + 1) / 2 * 2) : 0) +
-            (codes ? 64 * (size_t)mesh->nclass_host : (in_lds ? 64 * ncell_all : 0)) +
-            (lcodes ? sizeof(unsigned) * ((ncell_all + 1) / 2 * 2) : 0);
-        (void)hipMemsetAsync(n_handed, 0, sizeof(unsigned long long), ctx->stream);
-#define JB_LAUNCH_DDMC_ALL(TL, CO)                                                                          \
-  do {                                                                                                      \
-    /* (the dynamic LDS -- tally and record table of a small mesh -- changes with the mesh: ask per launch) */ \
-    int oc = 0;                                                                                             \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&oc, k_ddmc_all<NDIM, TL, CO>, kBlock, lds_tally_bytes) != hipSuccess || oc < 1) oc = 3; \
-    /* (four 16-byte loads per lane on a table that does not sit in L1 -- only a table of >= 4 GiB, or  \
-       JB_COOP_GATHER=0, gets here -- saturate the vector L1's look-ups: a fourth wave per SIMD then  \
-       costs time, 38.2 against 31.5 ms per 1e8 histories on the 160 MB table) */                      \
-    if ((CO) == 0 && rec_bytes >= (1ull << 20) && oc > 3) oc = 3;                                           \
-    const int g = grid_for(ctx, last - first, per_cu_env > 0 ? per_cu_env : oc);                            \
-    hipLaunchKernelGGL((k_ddmc_all<NDIM, TL, CO>), dim3(g), dim3(kBlock), lds_tally_bytes, ctx->stream, mesh->dm_dev, ctx->dp, S, \
-                       t_start, dt, first, last, ctx->counters_d, (const int *)M.not_all_ddmc, handed, n_handed); \
-  } while (0)
-#define JB_LAUNCH_DDMC_Q1(TL, LC)                                                                          \
-  do {                                                                                                      \
-    int oc = 0;                                                                                             \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&oc, k_ddmc_q<NDIM, TL, LC>, kBlock, lds_tally_bytes) != hipSuccess || oc < 1) oc = 3; \
-    const int g = grid_for(ctx, last - first, per_cu_env > 0 ? per_cu_env : oc);                            \
-    hipLaunchKernelGGL((k_ddmc_q<NDIM, TL, LC>), dim3(g), dim3(kBlock), lds_tally_bytes, ctx->stream, mesh->dm_dev, ctx->dp, S, \
-                       t_start, dt, first, last, ctx->counters_d, (const int *)M.not_all_ddmc, handed, n_handed); \
-  } while (0)
-#define JB_LAUNCH_DDMC_Q(TL)                                                                               \
-  do {                                                                                                      \
-    if (lcodes) JB_LAUNCH_DDMC_Q1(TL, true);                                                                \
-    else JB_LAUNCH_DDMC_Q1(TL, false);                                                                      \
-  } while (0)
-#define JB_LAUNCH_HANDED(TL, NA)                                                                            \
-  do {                                                                                                      \
-    (void)hipMemsetAsync(ctx->counters_d + CNT_QUEUE, 0, kQueues * kQueueStride * sizeof(unsigned long long), ctx->stream); \
-    hipLaunchKernelGGL((k_hybrid<NDIM, TL, NA, 0, 0>), dim3(kQueues), dim3(kBlock), 0, ctx->stream, mesh->dm_dev, \
-                       ctx->dp, S, t_start, dt, 0ll, (long long)(last - first), ctx->counters_d,            \
-                       (const unsigned *)handed, (unsigned *)nullptr, (unsigned long long *)nullptr,         \
-                       (const unsigned long long *)n_handed);                                               \
-  } while (0)
-        static const char *const names[3][2][4] = {
-            {{"k_ddmc_all<1, false>", "k_ddmc_all<1, false, quad gather>", "k_ddmc_all<1, false, records in LDS>", "k_ddmc_all<1, false, cell codes>"},
-             {"k_ddmc_all<1, true>", "k_ddmc_all<1, true, quad gather>", "k_ddmc_all<1, true, records in LDS>", "k_ddmc_all<1, true, cell codes>"}},
-            {{"k_ddmc_all<2, false>", "k_ddmc_all<2, false, quad gather>", "k_ddmc_all<2, false, records in LDS>", "k_ddmc_all<2, false, cell codes>"},
-             {"k_ddmc_all<2, true>", "k_ddmc_all<2, true, quad gather>", "k_ddmc_all<2, true, records in LDS>", "k_ddmc_all<2, true, cell codes>"}},
-            {{"k_ddmc_all<3, false>", "k_ddmc_all<3, false, quad gather>", "k_ddmc_all<3, false, records in LDS>", "k_ddmc_all<3, false, cell codes>"},
-             {"k_ddmc_all<3, true>", "k_ddmc_all<3, true, quad gather>", "k_ddmc_all<3, true, records in LDS>", "k_ddmc_all<3, true, cell codes>"}}};
-        static const char *const qnames[2][3][2] = {
-            {{"k_ddmc_all<1, false, cell codes, queues>", "k_ddmc_all<1, true, cell codes, queues>"},
-             {"k_ddmc_all<2, false, cell codes, queues>", "k_ddmc_all<2, true, cell codes, queues>"},
-             {"k_ddmc_all<3, false, cell codes, queues>", "k_ddmc_all<3, true, cell codes, queues>"}},
-            {{"k_ddmc_all<1, false, cell codes, queues, codes in LDS>", "k_ddmc_all<1, true, cell codes, queues, codes in LDS>"},
-             {"k_ddmc_all<2, false, cell codes, queues, codes in LDS>", "k_ddmc_all<2, true, cell codes, queues, codes in LDS>"},
-             {"k_ddmc_all<3, false, cell codes, queues, codes in LDS>", "k_ddmc_all<3, true, cell codes, queues, codes in LDS>"}}};
-        mesh->last_variant = queues ? qnames[lcodes ? 1 : 0][NDIM - 1][tally ? 1 : 0]
-                                    : names[NDIM - 1][tally ? 1 : 0][gather == 4 ? 3 : (gather == 3 ? 1 : gather)];
-        if (tally) {
-          if (queues) JB_LAUNCH_DDMC_Q(true);
-          else if (gather == 4) JB_LAUNCH_DDMC_ALL(true, 4);
-          else if (gather == 1) JB_LAUNCH_DDMC_ALL(true, 1);
-          else if (gather == 2) JB_LAUNCH_DDMC_ALL(true, 2);
-          else if (gather == 3) JB_LAUNCH_DDMC_ALL(true, 3);
-          else JB_LAUNCH_DDMC_ALL(true, 0);
-          if (noabs_h) JB_LAUNCH_HANDED(true, true);
-          else JB_LAUNCH_HANDED(true, false);
-        } else {
-          if (queues) JB_LAUNCH_DDMC_Q(false);
-          else if (gather == 4) JB_LAUNCH_DDMC_ALL(false, 4);
-          else if (gather == 1) JB_LAUNCH_DDMC_ALL(false, 1);
-          else if (gather == 2) JB_LAUNCH_DDMC_ALL(false, 2);
-          else if (gather == 3) JB_LAUNCH_DDMC_ALL(false, 3);
-          else JB_LAUNCH_DDMC_ALL(false, 0);
-          if (noabs_h) JB_LAUNCH_HANDED(false, true);
-          else JB_LAUNCH_HANDED(false, false);
-        }
-#undef JB_LAUNCH_HANDED
-#undef JB_LAUNCH_DDMC_Q
-#undef JB_LAUNCH_DDMC_Q1
-#undef JB_LAUNCH_DDMC_ALL
-        return JB_COMPLETE;
-      }
-      // A mix of IMC and DDMC cells, three launches: k_hybrid<.., PHASE 1> follows the photons in
-      // IMC cells (its service phase also takes the albedo step of a photon that enters a DDMC
-      // cell) and parks those that settle in DDMC cells; <.., PHASE 2> follows these and parks the
-      // ones that leak back into IMC cells; <.., PHASE 0>, which runs both event loops, finishes
-      // that remainder -- the photons that keep changing regime at the interface (alternating
-      // phases 1 and 2 until nothing is left costs one launch per change of regime of the most
-      // persistent photon: measured ~80 rounds of ~0.5 ms on BASELINE configs[4]).  The lists of
-      // parked photons (slot numbers, 4 bytes each) live in the context's scratch buffer.
-      // (variant string: NDIM, TALLY, NOABS, MODE: 0 exact arithmetic, 1 lean, 2 lean on exact geometry)
-      const long long nrange = last - first;
-      {  // 2 lists x 4 bytes x n
-        const jb_status st_s = ensure_scratch(ctx, (size_t)nrange + 16);
-        if (st_s != JB_COMPLETE) return st_s;
-      }
-      unsigned *list_d = (unsigned *)ctx->scratch_d;          // parked by phase 1, read by phase 2
-      unsigned *list_i = list_d + nrange;                     // parked by phase 2, read by phase 1
-      unsigned long long *cnt = ctx->counters_d + kCursorBase;  // [0] |list_d|, [1] |list_i|
-      volatile unsigned long long *cnt_h = ctx->counters_h + kCursorBase;
-#define JB_LAUNCH_H(T, NA, MD, PH, F, L, LIN, LOUT, COUT)                                          \
-  do {                                                                                             \
-    static int occ = 0;                                                                            \
-    if (occ < 1 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_hybrid<NDIM, T, NA, MD, PH>, \
-                                                                 kBlock, 0) != hipSuccess || occ < 1)) \
-      occ = 3;                                                                                     \
-    const int g = grid_for(ctx, (L) - (F), per_cu_env > 0 ? per_cu_env : occ);                     \
-    (void)hipMemsetAsync(ctx->counters_d + CNT_QUEUE, 0, kQueues * kQueueStride * sizeof(unsigned long long), ctx->stream); \
-    hipLaunchKernelGGL((k_hybrid<NDIM, T, NA, MD, PH>), dim3(g), dim3(kBlock), 0, ctx->stream,     \
-                       mesh->dm_dev, ctx->dp, S, t_start, dt, (long long)(F), (long long)(L), ctx->counters_d,   \
-                       (const unsigned *)(LIN), (unsigned *)(LOUT), (unsigned long long *)(COUT),  \
-                       (const unsigned long long *)nullptr);                                       \
-  } while (0)
-#define JB_PHASE1(T, NA, F, L, LIN)                                                                \
-  do {                                                                                             \
-    if (!ctx->lean_arith) JB_LAUNCH_H(T, NA, 0, 1, F, L, LIN, list_d, cnt);                        \
-    else if (mesh->exact_geom && mesh->cell_ok && !ctx->no_imc_cell) JB_LAUNCH_H(T, NA, 3, 1, F, L, LIN, list_d, cnt); \
-    else if (mesh->exact_geom) JB_LAUNCH_H(T, NA, 2, 1, F, L, LIN, list_d, cnt);                            \
-    else JB_LAUNCH_H(T, NA, 1, 1, F, L, LIN, list_d, cnt);                                         \
-  } while (0)
-      {
-        const bool cell = mesh->exact_geom && mesh->cell_ok && !ctx->no_imc_cell;
-        static const char *const hyb_names[3][4] = {
-            {"k_hybrid<1, exact>", "k_hybrid<1, lean>", "k_hybrid<1, lean, exact geometry>", "k_hybrid<1, lean, cell-local>"},
-            {"k_hybrid<2, exact>", "k_hybrid<2, lean>", "k_hybrid<2, lean, exact geometry>", "k_hybrid<2, lean, cell-local>"},
-            {"k_hybrid<3, exact>", "k_hybrid<3, lean>", "k_hybrid<3, lean, exact geometry>", "k_hybrid<3, lean, cell-local>"}};
-        mesh->last_variant = hyb_names[NDIM - 1][!ctx->lean_arith ? 0 : (cell ? 3 : (mesh->exact_geom ? 2 : 1))];
-      }
-#define JB_PHASE0(T, NA, L, LIN)                                                                   \
-  do {                                                                                             \
-    if (!ctx->lean_arith) JB_LAUNCH_H(T, NA, 0, 0, 0, L, LIN, nullptr, nullptr);                   \
-    else if (mesh->exact_geom && mesh->cell_ok && !ctx->no_imc_cell) JB_LAUNCH_H(T, NA, 3, 0, 0, L, LIN, nullptr, nullptr); \
-    else if (mesh->exact_geom) JB_LAUNCH_H(T, NA, 2, 0, 0, L, LIN, nullptr, nullptr);                       \
-    else JB_LAUNCH_H(T, NA, 1, 0, 0, L, LIN, nullptr, nullptr);                                    \
-  } while (0)
-      (void)hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned long long), ctx->stream);
-      if (tally) { if (noabs_h) JB_PHASE1(true, true, first, last, nullptr); else JB_PHASE1(true, false, first, last, nullptr); }
-      else { if (noabs_h) JB_PHASE1(false, true, first, last, nullptr); else JB_PHASE1(false, false, first, last, nullptr); }
-      (void)hipMemcpyAsync((void *)cnt_h, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
-      JB_HIP(hipStreamSynchronize(ctx->stream));
-      const long long n_d = (long long)cnt_h[0];
-      if (n_d == 0) return JB_COMPLETE;
-      if (tally) JB_LAUNCH_H(true, true, 0, 2, 0, n_d, list_d, list_i, cnt + 1);
-      else JB_LAUNCH_H(false, true, 0, 2, 0, n_d, list_d, list_i, cnt + 1);
-      (void)hipMemcpyAsync((void *)(cnt_h + 1), cnt + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
-      JB_HIP(hipStreamSynchronize(ctx->stream));
-      const long long n_i = (long long)cnt_h[1];
-      if (n_i == 0) return JB_COMPLETE;
-      if (tally) { if (noabs_h) JB_PHASE0(true, true, n_i, list_i); else JB_PHASE0(true, false, n_i, list_i); }
-      else { if (noabs_h) JB_PHASE0(false, true, n_i, list_i); else JB_PHASE0(false, false, n_i, list_i); }
-#undef JB_PHASE0
-#undef JB_PHASE1
-#undef JB_LAUNCH_H
-      return JB_COMPLETE;
-    }
+  // (the one input the device holds: whether every cell takes DDMC steps, and the number of distinct step
+  // records, as UpdateDerivedTransportFields left them)
+  if (ddmc && gray && M.ddmc_cell && M.nblocks <= kLdsBlocks && mesh->not_all_ddmc_host < 0) {
+    int *flag_h = (int *)(ctx->counters_h + kCounterWords - 1);
+    flag_h[0] = 1; flag_h[1] = 0;
+    (void)hipMemcpyAsync(flag_h, M.not_all_ddmc, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+    JB_HIP(hipStreamSynchronize(ctx->stream));
+    mesh->not_all_ddmc_host = flag_h[0] != 0 ? 1 : 0;
+    mesh->nclass_host = flag_h[1];
   }
-  // gray opacity with kappa = 0 (opacity_model = none): sigma_a = rho * 0 in every cell
-  const bool noabs = gray && ctx->dp.kappa_a == 0.0;
-  if (noabs) {
-    if (tally) JB_LAUNCH(true, 2);
-    else JB_LAUNCH(false, 2);
-    return JB_COMPLETE;
+  TransportInputs in;
+  in.ndim = NDIM;
+  in.ddmc = ddmc;
+  in.tally = tally;
+  in.gray = gray;
+  in.has_ddmc_cell = M.ddmc_cell != nullptr;
+  in.has_ddmc_code = M.ddmc_code != nullptr;
+  in.nblocks = M.nblocks;
+  in.ntot = M.ntot;
+  in.last = last;
+  in.not_all_ddmc = mesh->not_all_ddmc_host != 0;
+  in.nclass = mesh->nclass_host;
+  in.noabs = ctx->dp.kappa_a == 0.0;
+  in.exact_geom = mesh->exact_geom;
+  in.cell_ok = mesh->cell_ok;
+  in.uniform_geom = mesh->uniform_geom;
+  in.lean_arith = ctx->lean_arith;
+  in.no_imc_cell = ctx->no_imc_cell;
+  in.coop_gather = ctx->coop_gather;
+  in.ddmc_queues = ctx->ddmc_queues != 0;
+  in.ddmc_lds_codes = ctx->ddmc_lds_codes != 0;
+  in.max_classes = ctx->max_classes;
+  const TransportPlan plan = select_transport(in);
+  variant_name(plan, mesh->last_variant, sizeof mesh->last_variant);
+  switch (plan.family) {
+  case Family::k_transport: launch_k_transport<NDIM>(ctx, mesh, plan, S, t_start, dt, first, last); break;
+  case Family::k_imc_cell: launch_k_imc_cell<NDIM>(ctx, mesh, plan, S, t_start, dt, first, last); break;
+  case Family::k_ddmc_all:
+  case Family::k_ddmc_q: return launch_all_ddmc<NDIM>(ctx, mesh, plan, S, t_start, dt, first, last);
+  case Family::k_hybrid: return launch_mixed<NDIM>(ctx, mesh, plan, S, t_start, dt, first, last);
   }
-  if (tally && gray) JB_LAUNCH(true, 1);
-  else if (tally) JB_LAUNCH(true, 0);
-  else if (gray) JB_LAUNCH(false, 1);
-  else JB_LAUNCH(false, 0);
-#undef JB_LAUNCH
-#undef JB_LAUNCH_CELL
-#undef JB_LAUNCH_CELL_U
-#undef JB_LAUNCH_X
   return JB_COMPLETE;
 }
 
@@ -1359,14 +1281,9 @@ static jb_status transport_impl(jb_context *ctx, jb_mesh *mesh, const jb_swarm_v
   } else {
     ctx->tev_overflow = true;
   }
-  switch (M.ndim * 2 + (ddmc ? 1 : 0)) {
-  case 2: st = launch_transport<1, false>(ctx, mesh, S, t_start, dt, first, last, tl); break;
-  case 3: st = launch_transport<1, true>(ctx, mesh, S, t_start, dt, first, last, tl); break;
-  case 4: st = launch_transport<2, false>(ctx, mesh, S, t_start, dt, first, last, tl); break;
-  case 5: st = launch_transport<2, true>(ctx, mesh, S, t_start, dt, first, last, tl); break;
-  case 6: st = launch_transport<3, false>(ctx, mesh, S, t_start, dt, first, last, tl); break;
-  default: st = launch_transport<3, true>(ctx, mesh, S, t_start, dt, first, last, tl); break;
-  }
+  with_int<1, 2, 3>(M.ndim, [&](auto nd) {
+    st = launch_transport<decltype(nd)::value>(ctx, mesh, S, t_start, dt, first, last, tl, ddmc);
+  });
   if (ev_stop) (void)hipEventRecord(ev_stop, ctx->stream);
   if (st != JB_COMPLETE) return st;
   JB_HIP(hipGetLastError());

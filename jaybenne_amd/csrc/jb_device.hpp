@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "jb_limits.hpp"
 #include "jb_physics.hpp"
 
 namespace jb {
@@ -143,8 +144,7 @@ typedef const __attribute__((address_space(4))) struct DevMesh *MeshConstPtr;
 // (that kernel keeps the block index per lane, at most kLdsBlocks = 128 resident blocks); a DDMC
 // cell's datum there is negative too, with an ordinary exponent.
 constexpr int kGhostHi = (int)0xC3300000u, kGhostTable = 1 << 19;
-// cell codes of the all-DDMC kernel (DevMesh::ddmc_code)
-constexpr int kMaxClasses = 256;            // 16 KB of LDS per workgroup at most
+// cell codes of the all-DDMC kernel (DevMesh::ddmc_code; kMaxClasses: jb_limits.hpp)
 constexpr int kClassSlots = 4 * kMaxClasses;
 constexpr unsigned kCodeGhost = 0x80000000u, kCodeMirror = 0x40000000u, kCodeTable = 0x20000000u;
 constexpr unsigned kCodeRecMask = 0x1fffffffu;
@@ -202,10 +202,7 @@ __device__ __forceinline__ void load_block(const DevMesh &M, int b, Blk &B) {
 // The same from a copy of the per-block tables in LDS (kernels whose service phase would wait
 // for these small dependent loads behind its own stores: vector-memory operations complete in
 // issue order, LDS reads have their own counter).  Up to kLdsBlocks resident blocks.
-#ifndef JB_LDS_BLOCKS
-#define JB_LDS_BLOCKS 128
-#endif
-constexpr int kLdsBlocks = JB_LDS_BLOCKS;
+// (kLdsBlocks, and the JB_LDS_BLOCKS that overrides it: jb_limits.hpp)
 // (X0: also the coordinate of cell index 0, xmin - first dx, per block and axis -- 3 KB that
 // k_ddmc_all, which needs the room for a fourth workgroup per CU, forms where it reads it)
 template <bool X0, int NB = kLdsBlocks>

@@ -130,7 +130,6 @@ __device__ __forceinline__ unsigned quad_bcast_add(unsigned v, unsigned add) {
 // the table of BASELINE configs[2] in 3-D shrinks from 161 MB to 10 MB (what one XCD's photons touch:
 // from 1.8 MB to 110 KB -- L1 / L2 resident), the code for the NEXT pass is requested at the end of a pass,
 // and the workgroup's 16 KB landing buffer of the quad gather is not needed.
-constexpr int kLdsRecCells = 256;
 // (NDIM < 3) pd of a leak through the "z+" arm of transport_utils.hpp:254-263 on a mesh without a z axis
 // (xim rounds onto leak_tot: one event in ~1e16): the channel is z+, the cell does not change (:256,
 // kp += three_d)

@@ -27,8 +27,6 @@ namespace jb {
 
 constexpr int kQReady = 128;   // entries: up to 64 left over + 64 photons per fill (or re-entering after a relocation)
 constexpr int kQDone = 64;     // one full-width batch for the service phase
-constexpr int kQBlocks = 64;   // per-block tables in LDS (k_ddmc_all: 128): with the queues the workgroup stays under
-                               // 40 KB of LDS, i.e. four workgroups per CU
 #ifndef JB_DDMC_Q_RETIRE_MIN   // lanes without a running photon before the loop exchanges them (3-D / 2-D; 1-D: 1)
 #define JB_DDMC_Q_RETIRE_MIN 1
 #endif
@@ -50,7 +48,6 @@ struct WaveQueues {
 // as well, and the event loop has no vector-memory instruction left: its gather no longer queues in the CU's
 // vector L1 behind the scattered photon loads and stores of the other waves' service phases (measured on
 // BASELINE configs[2] as shipped: 910 of a pass's 2560 wave-cycles were that wait; the table is 544 bytes).
-constexpr int kLdsCodeCells = 1024;
 
 template <int NDIM, bool TALLY, bool LCODES = false>
 __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)

@@ -29,7 +29,6 @@ constexpr int kBlock = 256;  // 4 waves per workgroup
 
 // counters[]: 0 census, 1 absorbed, 2 escaped, 3 outgoing, 4 events, 5 unfinished
 enum { CNT_CENSUS = 0, CNT_ABSORBED, CNT_ESCAPED, CNT_OUTGOING, CNT_EVENTS, CNT_UNFINISHED, CNT_PASSES, CNT_SERVICE, CNT_N };
-constexpr int kLdsTally = 1024;  // cells (all resident blocks, ghosts included) tallied in LDS
 // Heads of the 8 particle queues of the running transport launch, each in a 128-byte line of its own: the claims
 // are returning atomics from every XCD, and atomics on one line are served one after the other -- with the eight
 // heads in ONE line (rounds 1 - 5) and 128-slot claims, BASELINE configs[2] as shipped (12-step histories: 7.8e5

@@ -1,0 +1,20 @@
+// jb_limits.hpp -- the mesh-size limits that the tracking kernels are compiled for and that the host's
+// kernel selection (jb_select.hpp) tests.  Plain C++: a host compiler reads it without HIP.
+#pragma once
+
+namespace jb {
+
+// resident blocks whose per-block tables a kernel keeps in LDS (LdsBlockTableT, jb_device.hpp)
+#ifndef JB_LDS_BLOCKS
+#define JB_LDS_BLOCKS 128
+#endif
+constexpr int kLdsBlocks = JB_LDS_BLOCKS;
+constexpr int kQBlocks = 64;   // ... of k_ddmc_q (k_ddmc_all: 128): with the queues the workgroup stays under
+                               // 40 KB of LDS, i.e. four workgroups per CU
+constexpr int kLdsTally = 1024;  // cells (all resident blocks, ghosts included) tallied in LDS
+// cell codes of the all-DDMC kernel (DevMesh::ddmc_code)
+constexpr int kMaxClasses = 256;            // 16 KB of LDS per workgroup at most
+constexpr int kLdsRecCells = 256;    // cells whose step records k_ddmc_all<.., GATHER 2> copies to LDS (jb_kernel_ddmc.hpp)
+constexpr int kLdsCodeCells = 1024;  // cells whose codes k_ddmc_q<.., LCODES> copies to LDS (jb_kernel_ddmc_q.hpp)
+
+}  // namespace jb
