@@ -577,6 +577,10 @@ int main(int argc, char **argv) {
 
     // (as the Python driver: the swarm sorted by block and cell after every k-th cycle; 0 = never)
     md.defrag_interval = (int)pin.GetOrAddInteger("jaybenne", "defrag_interval", -1);
+    // (as the Python driver: the census comb -- a cell that ends a cycle with more than
+    // ceil(census_comb_trigger * census_per_cell_max) photons comes out with census_per_cell_max; 0 = off)
+    md.comb_target = pin.GetOrAddInteger("jaybenne_amd", "census_per_cell_max", 0);
+    md.comb_trigger = jb::CombTrigger(md.comb_target, pin.GetOrAddReal("jaybenne_amd", "census_comb_trigger", 2.0));
     jb::InitializeRadiation(&md, initial_radiation == "thermal");
     // --ledger FILE (or <jaybenne_amd> ledger = true, or JB_LEDGER=1): the energy ledger of every cycle
     std::FILE *ledger_file = nullptr;
@@ -613,6 +617,9 @@ int main(int argc, char **argv) {
         std::printf(" leak=[%.6e, %.6e, %.6e, %.6e, %.6e, %.6e] residual=%.3e", l.e_escaped[0], l.e_escaped[1],
                     l.e_escaped[2], l.e_escaped[3], l.e_escaped[4], l.e_escaped[5], l.residual);
       }
+      if (!md.comb_history.empty() && md.comb_history.back().cycle == (int64_t)md.cycle)
+        std::printf(" combed=%lld new_ids=%lld", (long long)md.comb_history.back().cells_combed,
+                    (long long)md.comb_history.back().n_new_ids);
       std::printf("\n");
     }
     if (ledger_file) std::fclose(ledger_file);

@@ -380,6 +380,59 @@ jb_status jb_defrag_policy(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *
  * then skips the sort with a message on stderr and stops asking. */
 jb_status jb_release_scratch(jb_context *ctx);
 
+/* Census population control: an energy-conserving comb per cell (the reference has none: nothing there ever
+ * reduces the number of photons, and a deck with do_emission adds num_particles per cycle).  Called between two
+ * cycles.  A cell that holds more than trigger_T ACTIVE photons comes out with exactly target_K,
+ * 1 <= target_K <= trigger_T; every other cell, and every slot that is not ACTIVE, is left bit for bit as it was.
+ * For a combed cell with photons j = 1..m in the slot order the sort left them, W = sum w_j, D = W / K,
+ * C_j = w_1 + .. + w_j and xi one uniform in (0,1) per cell and epoch:
+ *     u_0 = 0,   u_j = clamp(ceil(C_j / D - xi), 0, K) for j < m,   u_m = K,
+ * and photon j comes out as k_j = u_j - u_(j-1) copies of weight D.  sum k_j = K; k_j is floor(w_j / D) or
+ * ceil(w_j / D); the expectation of k_j D over xi is w_j; the cell's energy is conserved to rounding.
+ * A copy carries everything its original carries (position, direction, time, e, indices, block, status).  The
+ * first copy also keeps id and stream state; every further copy takes the next unused creation id -- handed out in
+ * output-slot order over the call, from id_base -- and starts that id's stream (what the source gives a new
+ * photon, so the streams stay disjoint).
+ *     xi = uniform of the state  seed_state(seed, domain 2, epoch << 44 | global block id << 24 | cell),
+ * cell = the cell's index in the block's array (ghost cells included, < 2^24), epoch < 2^20 the cycle number:
+ * the draw does not depend on how the blocks are dealt to ranks.
+ * A cell whose weight is not positive and finite is left alone.  Weights are taken to be non-negative.
+ *
+ * jb_comb_census_plan sorts the swarm by (block, cell) -- jb_defrag_particles; slots that are not ACTIVE end up
+ * behind all cells; a swarm that is in that order already is not moved, so the same sorted swarm gives the same
+ * bits --, forms the running weights with a segmented scan, decides k_j for every slot and reads
+ * back the plan; it synchronises the stream.  Nothing a photon carries has changed yet.  When no cell exceeds
+ * trigger_T, n_after == n_before and cells_combed == 0: the host skips jb_comb_census_apply.  For the schedule of
+ * jb_defrag_policy a plan that sorted counts as a sort (the policy starts over from the sorted order; the sort's cost per
+ * photon it keeps is that of the last sort it timed itself).
+ * jb_comb_census_apply moves survivors and copies into a compact swarm that is still in (block, cell) order,
+ * sets swarm->n (n_after <= n_before: the call never needs capacity) and reports the census energy behind it,
+ * summed in a fixed order; it synchronises too.  The plan lives in the library's scratch memory: no other call
+ * that uses this context may come between the two.
+ * Which photons of a cell survive depends on the order the sort left them in, which is arbitrary within a cell:
+ * counts, energies per cell and the distribution do not differ from run to run, the surviving ids can.
+ * JB_ERR_INVALID: target_K < 1, target_K > trigger_T, trigger_T >= 2^32, epoch >= 2^20, the limits of
+ * jb_defrag_particles (2^32 - 1 photons, 2^32 - 2 cells), apply without a plan for this swarm.  Scratch: what the
+ * sort takes plus 16 bytes per photon; if it cannot be allocated, JB_ERR_HIP and the swarm is as it was. */
+typedef struct jb_comb_plan {
+  int64_t n_before;      /* swarm->n */
+  int64_t n_after;       /* ... behind jb_comb_census_apply */
+  int64_t n_new_ids;     /* creation ids apply hands out: id_base .. id_base + n_new_ids - 1 */
+  int64_t cells_combed;
+  int64_t max_per_cell;  /* most ACTIVE photons in one cell, before the comb */
+  double e_before;       /* weight of the ACTIVE photons, summed in a fixed order */
+  int64_t sorted;        /* 1: the plan sorted the swarm; 0: it was in (block, cell) order already */
+} jb_comb_plan;
+typedef struct jb_comb_report {
+  int64_t n_after;
+  int64_t n_new_ids;
+  double e_after;        /* weight of the ACTIVE photons behind the comb, summed in the same order */
+} jb_comb_report;
+jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, int64_t trigger_T,
+                              int64_t target_K, uint32_t epoch, jb_comb_plan *out);
+jb_status jb_comb_census_apply(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, uint64_t id_base,
+                               jb_comb_report *out);
+
 /* MeshSend / MeshReceive (jaybenne.cpp:36-61) for the inter-rank part: OUTGOING particles are
  * among [first,last) are copied into fixed-size records (JB_RECORD_WORDS x 8 bytes), ordered by
  * destination rank, and their slots are re-marked JB_ST_ABSORBED-like holes (status

@@ -96,6 +96,13 @@ inline std::shared_ptr<StateDescriptor> Initialize(const jb_params &p, const jb_
 struct EnergyLedger : jb_energy_ledger {
   double e_start = 0.0, residual = 0.0;
 };
+// one combed cycle (MeshData::comb_history; the keys of the Python host's md.comb_history)
+struct CombRecord {
+  int64_t cycle, n_before, n_after, n_new_ids;
+  uint64_t id_base;
+  int64_t cells_combed, max_per_cell;
+  double e_before, e_after;
+};
 inline double LedgerResidual(const jb_energy_ledger &l, double e_start) {
   const double lhs = e_start + l.e_sourced;
   double r = lhs - l.e_census;
@@ -157,6 +164,10 @@ class MeshData {
   std::vector<EnergyLedger> ledger_history;
   bool ledger_started = false;  // ledger_e0 holds the census energy the next cycle starts from
   double ledger_e0 = 0.0;
+  // census comb (CombCensus; jaybenne_amd.h: jb_comb_census_plan): a cell that ends a cycle with more than
+  // comb_trigger photons comes out with comb_target; 0 = off (the reference: no population control)
+  int64_t comb_target = 0, comb_trigger = 0;
+  std::vector<CombRecord> comb_history;   // one record per cycle whose comb changed the swarm
 
  private:
   std::shared_ptr<StateDescriptor> pkg_;
@@ -165,6 +176,14 @@ class MeshData {
   int32_t *prefix_dev_;
   std::function<void(jb_swarm_view &, int64_t)> reserve_;
 };
+
+// T = ceil(trigger K) of the deck keys <jaybenne_amd> census_per_cell_max = K and census_comb_trigger (every
+// host forms it this way)
+inline int64_t CombTrigger(int64_t target, double trigger) {
+  if (target < 0) throw std::invalid_argument("census_per_cell_max must be >= 0");
+  if (!(trigger >= 1.0)) throw std::invalid_argument("census_comb_trigger must be >= 1");
+  return (int64_t)std::ceil(trigger * (double)target);
+}
 
 // ---- host-side arithmetic of SourcePhotons shared by every host (this header's single-rank tasks,
 // examples/handoff_mpi.cpp across MPI ranks, adapters/parthenon/jaybenne_amd_tasks.cpp) ----------
@@ -575,6 +594,35 @@ inline void DefragAfterStep(MeshData *md, int64_t events) {
   }
 }
 
+// Census population control at the end of a cycle, single process (not in the reference's task list): every cell
+// with more than md->comb_trigger ACTIVE photons comes out with exactly md->comb_target of equal weight, its
+// energy kept (jaybenne_amd.h: jb_comb_census_plan / _apply).  New creation ids come from md->next_id.  Returns
+// true when the plan sorted the swarm.
+inline bool CombCensus(MeshData *md) {
+  if (md->comb_target <= 0) return false;
+  jb_comb_plan plan{};
+  Check(jb_comb_census_plan(md->ctx(), md->mesh(), &md->swarm, md->comb_trigger, md->comb_target, (uint32_t)md->cycle,
+                            &plan));
+  if (plan.cells_combed > 0) {
+    jb_comb_report rep{};
+    Check(jb_comb_census_apply(md->ctx(), md->mesh(), &md->swarm, md->next_id, &rep));
+    md->comb_history.push_back(CombRecord{(int64_t)md->cycle, plan.n_before, rep.n_after, rep.n_new_ids, md->next_id,
+                                          plan.cells_combed, plan.max_per_cell, plan.e_before, rep.e_after});
+    md->next_id += (uint64_t)rep.n_new_ids;
+  }
+  return plan.sorted != 0;
+}
+// the end of a cycle: the comb where it is on, then DefragParticles' schedule.  A cycle whose comb sorted the
+// swarm counts as a sort: the k-th-cycle counter starts over; the library's schedule has started over inside
+// the plan and is still called (it reads the cycle's kernel times and, one cycle behind a sort, never sorts).
+inline void CombAfterStep(MeshData *md, int64_t events) {
+  if (CombCensus(md) && md->defrag_interval >= 0) {
+    md->steps_since_defrag = 0;
+    return;
+  }
+  DefragAfterStep(md, events);
+}
+
 // ---- energy ledger (jaybenne_amd.h: jb_ledger_*): off by default ----------------------------------
 inline bool LedgerEnabled(MeshData *md) { return jb_ledger_enabled(md->ctx()) == 1; }
 inline void EnableLedger(MeshData *md, bool on = true) {
@@ -656,7 +704,7 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt)
     led.cycle = (int64_t)md->cycle;
     LedgerRecord(md, led);
   }
-  DefragAfterStep(md, after.n_events - before.n_events);
+  CombAfterStep(md, after.n_events - before.n_events);
   return TaskStatus::complete;
 }
 

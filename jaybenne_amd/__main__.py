@@ -87,6 +87,8 @@ def main(argv=None) -> int:
                 led = drv.md.ledger
                 ledger_file.write(ledger_json(led) + "\n")
                 line += " leak=[" + ", ".join(f"{e:.6e}" for e in led["e_escaped"]) + f"] residual={led['residual']:.3e}"
+            if drv.md.comb_history and drv.md.comb_history[-1]["cycle"] == drv.md.cycle:
+                line += f" combed={drv.md.comb_history[-1]['cells_combed']} new_ids={drv.md.comb_history[-1]['n_new_ids']}"
             print(line)
     except JaybenneError as e:
         if not (checked and e.status == JB_ERR_INVARIANT):

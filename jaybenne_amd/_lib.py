@@ -189,6 +189,17 @@ def ledger_residual(led: dict, e_start: float) -> float:
     return abs(res) / lhs if lhs > 0.0 else 0.0
 
 
+# jb_comb_plan / jb_comb_report (include/jaybenne_amd.h): the census comb
+class CombPlan(C.Structure):
+    _fields_ = [("n_before", C.c_int64), ("n_after", C.c_int64), ("n_new_ids", C.c_int64),
+                ("cells_combed", C.c_int64), ("max_per_cell", C.c_int64), ("e_before", C.c_double),
+                ("sorted", C.c_int64)]
+
+
+class CombReport(C.Structure):
+    _fields_ = [("n_after", C.c_int64), ("n_new_ids", C.c_int64), ("e_after", C.c_double)]
+
+
 # every entry point include/jaybenne_amd.h declares: name -> (restype, argtypes)
 _vp, _i64, _f64, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
 PROTOTYPES = {
@@ -224,6 +235,8 @@ PROTOTYPES = {
     "jb_remove_marked_particles": (_int, [_vp, C.POINTER(SwarmView)]),
     "jb_defrag_particles": (_int, [_vp, _vp, C.POINTER(SwarmView)]),
     "jb_release_scratch": (_int, [_vp]),
+    "jb_comb_census_plan": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, _i64, C.c_uint32, C.POINTER(CombPlan)]),
+    "jb_comb_census_apply": (_int, [_vp, _vp, C.POINTER(SwarmView), C.c_uint64, C.POINTER(CombReport)]),
     "jb_defrag_policy": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, C.c_int32, C.POINTER(C.c_int32)]),
     "jb_pack_outgoing": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, _i64, _int, _vp, _i64, _vp]),
     "jb_unpack_incoming": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, _i64]),

@@ -24,6 +24,7 @@
 #include "jb_kernel_ddmc_q.hpp"
 #include "jb_kernel_imc.hpp"
 #include "jb_kernel_ledger.hpp"
+#include "jb_kernel_comb.hpp"
 #include "jb_select.hpp"
 
 using namespace jb;
@@ -68,6 +69,17 @@ struct jb_context {
                                               // | (checked build) this rank's invariant violations since its last exchange
   long long inv_reported = 0;                 // (checked build) the violation count the last jb_exchange reported
   size_t scratch_words = 0;
+  unsigned long long scratch_gen = 0;         // counts the (re)allocations and releases of scratch_d
+  // jb_comb_census_plan -> jb_comb_census_apply: the plan lies in scratch_d
+  struct {
+    bool valid = false;
+    const jb_mesh *mesh = nullptr;
+    const double *x = nullptr;                // the swarm it was made for
+    long long n = 0, n_after = 0, n_new = 0;
+    unsigned T = 0, K = 0;
+    int ends_shift = 0;                       // the cells' ends are the histogram array from this entry on
+    unsigned long long gen = 0;
+  } comb;
   // jb_radiation_step_ranks: the hand-off record buffers (JB_RECORD_WORDS words per record) and the buffer of
   // the step's first all-gather ([status | counts per global block] of this rank, then every rank's)
   long long *step_send_d = nullptr, *step_recv_d = nullptr;
@@ -358,6 +370,7 @@ static jb_status ensure_scratch(jb_context *ctx, size_t words, bool slack = true
   if (ctx->scratch_d) JB_HIP(hipFree(ctx->scratch_d));
   ctx->scratch_d = nullptr;
   ctx->scratch_words = 0;
+  ++ctx->scratch_gen;
   const size_t want = slack ? words + words / 4 + 1024 : words + 16;
   const hipError_t e = hipMalloc(&ctx->scratch_d, want * sizeof(long long));
   if (e != hipSuccess) {   // (told apart from every other failure: DefragParticles may go without its scratch)
@@ -1521,6 +1534,12 @@ extern "C" jb_status jb_remove_marked_particles(jb_context *ctx, jb_swarm_view *
   return JB_COMPLETE;
 }
 
+// scratch of the sort, in 8-byte words: the particle records (16 words each, on a 128-byte boundary), then
+// histogram / offsets (nbins), tile sums (ntiles) and keys (n), 4 bytes each
+static size_t sort_scratch_words(long long n, long long nbins, int ntiles) {
+  return (size_t)kSortRecWords * (size_t)n + (size_t)((nbins + ntiles + n) / 2 + 16);
+}
+
 extern "C" jb_status jb_defrag_particles(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm) {
   JB_RANGE("Jaybenne::DefragParticles");
   if (!ctx || !mesh) return fail(JB_ERR_INVALID, "null argument");
@@ -1536,10 +1555,8 @@ extern "C" jb_status jb_defrag_particles(jb_context *ctx, jb_mesh *mesh, const j
   const unsigned nkeys = (unsigned)nkeys64;
   const long long nbins = (long long)nkeys + 1;                       // + the bin behind all cells
   const int ntiles = (int)((nbins + kScanTile - 1) / kScanTile);
-  // scratch: the particle records (16 words each, on a 128-byte boundary), then histogram / offsets
-  // (nbins), tile sums (ntiles) and keys (n), 4 bytes each
   const size_t rec_words = (size_t)kSortRecWords * (size_t)n;
-  st = ensure_scratch(ctx, rec_words + (size_t)((nbins + ntiles + n) / 2 + 16), /*slack=*/false);
+  st = ensure_scratch(ctx, sort_scratch_words(n, nbins, ntiles), /*slack=*/false);
   if (st != JB_COMPLETE) return st;
   unsigned long long *rec = (unsigned long long *)ctx->scratch_d;
   unsigned *hist = (unsigned *)(rec + rec_words);
@@ -1557,6 +1574,206 @@ extern "C" jb_status jb_defrag_particles(jb_context *ctx, jb_mesh *mesh, const j
                      (const unsigned long long *)rec);
   JB_HIP(hipGetLastError());
   return JB_COMPLETE;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Census comb (jb_kernel_comb.hpp).  Scratch behind the sort's: C (n doubles), kcnt / extra (n + 1 words of 4
+// bytes each; the scans turn them into output slots and id offsets), the scans' tile sums, the partial sums.
+constexpr int kCombParts = 1024;   // workgroups of k_comb_cells / k_comb_energy at the most
+struct CombScratch {
+  unsigned long long *rec;
+  unsigned *ends, *key, *kcnt, *extra, *ssum, *tflag;
+  double *C, *tsum, *epart;
+  unsigned long long *cpart;
+  int ntiles;      // tiles of kScanTile over the n + 1 slots
+  size_t words;
+};
+static CombScratch comb_scratch(const jb_context *ctx, long long n, long long nbins) {
+  CombScratch c{};
+  const int sort_tiles = (int)((nbins + kScanTile - 1) / kScanTile);
+  c.ntiles = (int)((n + 1 + kScanTile - 1) / kScanTile);
+  const size_t nt = (size_t)c.ntiles, half = (size_t)(n + 2) / 2;
+  // offsets in 8-byte words from the start of the scratch memory (the sort's part: the layout of jb_defrag_particles)
+  size_t o = sort_scratch_words(n, nbins, sort_tiles);
+  const size_t oC = o; o += (size_t)n;
+  const size_t okcnt = o; o += half;
+  const size_t oextra = o; o += half;
+  const size_t ossum = o; o += (nt + 1) / 2;
+  const size_t otsum = o; o += nt;
+  const size_t otflag = o; o += (nt + 1) / 2;
+  const size_t ocpart = o; o += 2 * kCombParts;
+  const size_t oepart = o; o += kCombParts;
+  c.words = o;
+  unsigned long long *base = (unsigned long long *)ctx->scratch_d;
+  if (!base) return c;   // (asked for the size alone)
+  c.rec = base;
+  c.ends = (unsigned *)(base + (size_t)kSortRecWords * (size_t)n);
+  c.key = c.ends + nbins + sort_tiles;
+  c.C = (double *)(base + oC);
+  c.kcnt = (unsigned *)(base + okcnt);
+  c.extra = (unsigned *)(base + oextra);
+  c.ssum = (unsigned *)(base + ossum);
+  c.tsum = (double *)(base + otsum);
+  c.tflag = (unsigned *)(base + otflag);
+  c.cpart = base + ocpart;
+  c.epart = (double *)(base + oepart);
+  return c;
+}
+static int comb_parts(long long n) {
+  const long long b = (n + kBlock - 1) / kBlock;
+  return (int)(b < 1 ? 1 : (b > kCombParts ? kCombParts : b));
+}
+// the weight of the ACTIVE slots of [0, n): per-workgroup sums on the device, added here in workgroup order
+static jb_status comb_energy(jb_context *ctx, const DevSwarm &S, long long n, double *epart_d, double *out) {
+  *out = 0.0;
+  if (n <= 0) return JB_COMPLETE;
+  const int g = comb_parts(n);
+  std::vector<double> part((size_t)g);
+  hipLaunchKernelGGL(k_comb_energy, dim3(g), dim3(kBlock), 0, ctx->stream, S, n, epart_d);
+  JB_HIP(hipGetLastError());
+  JB_HIP(hipMemcpyAsync(part.data(), epart_d, sizeof(double) * (size_t)g, hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  double e = 0.0;
+  for (int q = 0; q < g; ++q) e += part[(size_t)q];
+  *out = e;
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, int64_t trigger_T,
+                                         int64_t target_K, uint32_t epoch, jb_comb_plan *out) {
+  JB_RANGE("Jaybenne::CombCensus");
+  if (!ctx || !mesh || !out) return fail(JB_ERR_INVALID, "jb_comb_census_plan: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  ctx->comb.valid = false;
+  jb_status st = check_swarm(swarm, "jb_comb_census_plan");
+  if (st != JB_COMPLETE) return st;
+  if (target_K < 1 || target_K > trigger_T)
+    return fail(JB_ERR_INVALID, "jb_comb_census_plan: target_K = %lld outside [1, trigger_T = %lld]", (long long)target_K,
+                (long long)trigger_T);
+  if (trigger_T >= (1ll << 32)) return fail(JB_ERR_INVALID, "jb_comb_census_plan: trigger_T beyond 2^32 - 1");
+  if (epoch >= (1u << 20)) return fail(JB_ERR_INVALID, "jb_comb_census_plan: epoch %u beyond 2^20 - 1", epoch);
+  memset(out, 0, sizeof *out);
+  const long long n = swarm->n;
+  out->n_before = out->n_after = n;
+  if (n == 0) return JB_COMPLETE;
+  if (n >= (1ll << 32)) return fail(JB_ERR_INVALID, "jb_comb_census_plan: more than 2^32 - 1 particles");
+  const DevMesh &M = mesh->dm;
+  const unsigned long long nkeys64 = (unsigned long long)M.nblocks * (unsigned long long)M.ntot;
+  if (nkeys64 >= (1ull << 32) - 1ull) return fail(JB_ERR_INVALID, "jb_comb_census_plan: more than 2^32 - 2 cells");
+  const unsigned nkeys = (unsigned)nkeys64;
+  const long long nbins = (long long)nkeys + 1;
+  // (all of the scratch first: the sort then finds room, and a failed allocation leaves the swarm as it was)
+  st = ensure_scratch(ctx, comb_scratch(ctx, n, nbins).words, /*slack=*/false);
+  if (st != JB_COMPLETE) return st;
+  const CombScratch c = comb_scratch(ctx, n, nbins);
+  const DevSwarm S = dev_swarm(swarm);
+  const unsigned T = (unsigned)trigger_T, K = (unsigned)target_K;
+  const int gn = grid_for(ctx, n), gc = comb_parts((long long)nkeys), nt = c.ntiles;
+  // In key order already (behind a DefragParticles, or a comb, that nothing has moved since)?  Then the sort's
+  // move is left out -- and the order within a cell, which the move leaves to its atomics, stays the caller's:
+  // the same sorted swarm then gives the same bits.
+  unsigned unsorted = 0u;
+  unsigned *flag_d = (unsigned *)c.cpart;
+  JB_HIP(hipMemsetAsync(flag_d, 0, sizeof(unsigned), ctx->stream));
+  hipLaunchKernelGGL(k_comb_keys, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, c.key);
+  hipLaunchKernelGGL(k_comb_unsorted, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key, n, flag_d);
+  JB_HIP(hipGetLastError());
+  JB_HIP(hipMemcpyAsync(&unsorted, flag_d, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  const unsigned *ends = c.ends;
+  if (unsorted) {
+    st = jb_defrag_particles(ctx, mesh, swarm);
+    if (st != JB_COMPLETE) return st;
+    // the schedule of jb_defrag_policy starts over from a sorted swarm (as behind defrag_now; this sort is not
+    // the one whose time the policy weighs against the kernels' loss)
+    ctx->rate_ref = 0.0;
+    ctx->rate_before_sort = 0.0;
+    ctx->excess_ms = 0.0;
+    ctx->cycles_since_sort = 0;
+    out->sorted = 1;
+    hipLaunchKernelGGL(k_comb_keys, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, c.key);
+  } else {   // the histogram and its scan alone: the cells' starts, the ends one entry on
+    const int sort_tiles = (int)((nbins + kScanTile - 1) / kScanTile);
+    unsigned *hist = c.ends, *sums = hist + nbins;
+    JB_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned) * (size_t)nbins, ctx->stream));
+    hipLaunchKernelGGL(k_sort_count, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, c.key, hist);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(sort_tiles), dim3(kBlock), 0, ctx->stream, hist, nbins, sums);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums, sort_tiles);
+    hipLaunchKernelGGL(k_scan_add, dim3(sort_tiles), dim3(kBlock), 0, ctx->stream, hist, nbins, (const unsigned *)sums);
+    ends = hist + 1;
+  }
+  hipLaunchKernelGGL(k_comb_seg_tiles, dim3(nt), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key,
+                     (const double *)S.w, n, c.C, c.tsum, c.tflag);
+  hipLaunchKernelGGL(k_comb_seg_sums, dim3(1), dim3(1024), 0, ctx->stream, c.tsum, (const unsigned *)c.tflag, nt);
+  hipLaunchKernelGGL(k_comb_seg_add, dim3(nt), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key, n, c.C,
+                     (const double *)c.tsum);
+  hipLaunchKernelGGL(k_comb_decide, dim3(grid_for(ctx, n + 1)), dim3(kBlock), 0, ctx->stream, M, n, nkeys,
+                     (const unsigned *)c.key, ends, (const double *)c.C, T, K, ctx->dp.key0, epoch,
+                     c.kcnt, c.extra);
+  hipLaunchKernelGGL(k_comb_cells, dim3(gc), dim3(kBlock), 0, ctx->stream, nkeys, ends, (const double *)c.C, T, c.cpart);
+  for (unsigned *data : {c.kcnt, c.extra}) {
+    hipLaunchKernelGGL(k_scan_tiles, dim3(nt), dim3(kBlock), 0, ctx->stream, data, n + 1, c.ssum);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, c.ssum, nt);
+    hipLaunchKernelGGL(k_scan_add, dim3(nt), dim3(kBlock), 0, ctx->stream, data, n + 1, (const unsigned *)c.ssum);
+  }
+  JB_HIP(hipGetLastError());
+  unsigned totals[2] = {0u, 0u};
+  std::vector<unsigned long long> cpart((size_t)(2 * gc));
+  JB_HIP(hipMemcpyAsync(&totals[0], c.kcnt + n, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipMemcpyAsync(&totals[1], c.extra + n, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipMemcpyAsync(cpart.data(), c.cpart, sizeof(unsigned long long) * cpart.size(), hipMemcpyDeviceToHost, ctx->stream));
+  st = comb_energy(ctx, S, n, c.epart, &out->e_before);   // (synchronises)
+  if (st != JB_COMPLETE) return st;
+  out->n_after = (long long)totals[0];
+  out->n_new_ids = (long long)totals[1];
+  for (int q = 0; q < gc; ++q) {
+    out->cells_combed += (int64_t)cpart[(size_t)(2 * q)];
+    if ((int64_t)cpart[(size_t)(2 * q + 1)] > out->max_per_cell) out->max_per_cell = (int64_t)cpart[(size_t)(2 * q + 1)];
+  }
+  if (out->n_after > n)   // (K <= T rules it out unless a running weight falls: the move must not go past the records)
+    return fail(JB_ERR_INVALID, "jb_comb_census_plan: the comb would grow the swarm (%lld -> %lld): negative weights?",
+                n, (long long)out->n_after);
+  ctx->comb.valid = true;
+  ctx->comb.mesh = mesh;
+  ctx->comb.x = swarm->x;
+  ctx->comb.n = n;
+  ctx->comb.n_after = out->n_after;
+  ctx->comb.n_new = out->n_new_ids;
+  ctx->comb.T = T;
+  ctx->comb.K = K;
+  ctx->comb.gen = ctx->scratch_gen;
+  ctx->comb.ends_shift = unsorted ? 0 : 1;
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_comb_census_apply(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, uint64_t id_base,
+                                          jb_comb_report *out) {
+  JB_RANGE("Jaybenne::CombCensus");
+  if (!ctx || !mesh || !out) return fail(JB_ERR_INVALID, "jb_comb_census_apply: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  jb_status st = check_swarm(swarm, "jb_comb_census_apply");
+  if (st != JB_COMPLETE) return st;
+  if (!ctx->comb.valid || ctx->comb.mesh != mesh || ctx->comb.x != swarm->x || ctx->comb.n != swarm->n ||
+      ctx->comb.gen != ctx->scratch_gen || !ctx->scratch_d)
+    return fail(JB_ERR_INVALID, "jb_comb_census_apply: no plan for this swarm (jb_comb_census_plan comes first)");
+  ctx->comb.valid = false;
+  const long long n = ctx->comb.n, n_after = ctx->comb.n_after;
+  const DevMesh &M = mesh->dm;
+  const unsigned nkeys = (unsigned)((unsigned long long)M.nblocks * (unsigned long long)M.ntot);
+  const CombScratch c = comb_scratch(ctx, n, (long long)nkeys + 1);
+  const DevSwarm S = dev_swarm(swarm);
+  hipLaunchKernelGGL(k_comb_pack, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream, S, n, nkeys,
+                     (const unsigned *)c.key, (const unsigned *)c.ends + ctx->comb.ends_shift, (const double *)c.C,
+                     (const unsigned *)c.kcnt,
+                     (const unsigned *)c.extra, ctx->comb.T, ctx->comb.K, ctx->dp.key0, (unsigned long long)id_base, c.rec);
+  if (n_after > 0)
+    hipLaunchKernelGGL(k_sort_unpack, dim3(grid_for(ctx, n_after)), dim3(kBlock), 0, ctx->stream, S, n_after,
+                       (const unsigned long long *)c.rec);
+  JB_HIP(hipGetLastError());
+  swarm->n = n_after;
+  out->n_after = n_after;
+  out->n_new_ids = ctx->comb.n_new;
+  return comb_energy(ctx, S, n_after, c.epart, &out->e_after);
 }
 
 // the sort of jb_defrag_policy, timed, and the policy's state behind it
@@ -1598,6 +1815,7 @@ extern "C" jb_status jb_release_scratch(jb_context *ctx) {
   if (ctx->scratch_d) JB_HIP(hipFree(ctx->scratch_d));
   ctx->scratch_d = nullptr;
   ctx->scratch_words = 0;
+  ++ctx->scratch_gen;
   if (ctx->step_send_d) JB_HIP(hipFree(ctx->step_send_d));
   if (ctx->step_recv_d) JB_HIP(hipFree(ctx->step_recv_d));
   if (ctx->step_gather_d) JB_HIP(hipFree(ctx->step_gather_d));

@@ -1591,6 +1591,22 @@ __device__ __forceinline__ void run_of(unsigned key, bool active, int lane, int 
   const int nact = __popcll(act);                                            // (active lanes: 0 .. nact-1)
   len = (above != 0ull ? __ffsll((long long)above) - 1 : nact) - head;
 }
+// sort_key: (resident block, cell of the position) of slot p as one word; nkeys for anything but an
+// ACTIVE photon in a resident block (behind all cells)
+__device__ __forceinline__ unsigned sort_key(const DevMesh &M, const DevSwarm &S, long long p, unsigned nkeys) {
+  const int b = S.blk[p];
+  if (S.status[p] != ST_ACTIVE || b < 0 || b >= M.nblocks) return nkeys;
+  Blk B;
+  load_block(M, b, B);
+  int i, j, kk;
+  if (M.ndim == 1) xtoijk<1>(M, B, S.x[p], S.y[p], S.z[p], i, j, kk);
+  else if (M.ndim == 2) xtoijk<2>(M, B, S.x[p], S.y[p], S.z[p], i, j, kk);
+  else xtoijk<3>(M, B, S.x[p], S.y[p], S.z[p], i, j, kk);
+  i = i < 0 ? 0 : (i >= M.ni ? M.ni - 1 : i);
+  j = j < 0 ? 0 : (j >= M.nj ? M.nj - 1 : j);
+  kk = kk < 0 ? 0 : (kk >= M.nk ? M.nk - 1 : kk);
+  return (unsigned)b * (unsigned)M.ntot + (unsigned)cidx(M, kk, j, i);
+}
 __global__ void __launch_bounds__(kBlock)
     k_sort_count(DevMesh M, DevSwarm S, long long n, unsigned nkeys, unsigned *key, unsigned *hist) {
   const int lane = threadIdx.x & 63;
@@ -1598,21 +1614,9 @@ __global__ void __launch_bounds__(kBlock)
   for (long long base = wave0; base < n; base += (long long)gridDim.x * blockDim.x) {
     const long long p = base + lane;
     const bool active = p < n;
-    unsigned k = nkeys;  // (anything but an active photon in a resident block: behind all cells)
+    unsigned k = nkeys;
     if (active) {
-      const int b = S.blk[p];
-      if (S.status[p] == ST_ACTIVE && b >= 0 && b < M.nblocks) {
-        Blk B;
-        load_block(M, b, B);
-        int i, j, kk;
-        if (M.ndim == 1) xtoijk<1>(M, B, S.x[p], S.y[p], S.z[p], i, j, kk);
-        else if (M.ndim == 2) xtoijk<2>(M, B, S.x[p], S.y[p], S.z[p], i, j, kk);
-        else xtoijk<3>(M, B, S.x[p], S.y[p], S.z[p], i, j, kk);
-        i = i < 0 ? 0 : (i >= M.ni ? M.ni - 1 : i);
-        j = j < 0 ? 0 : (j >= M.nj ? M.nj - 1 : j);
-        kk = kk < 0 ? 0 : (kk >= M.nk ? M.nk - 1 : kk);
-        k = (unsigned)b * (unsigned)M.ntot + (unsigned)cidx(M, kk, j, i);
-      }
+      k = sort_key(M, S, p, nkeys);
       key[p] = k;
     }
     int head, len;

@@ -48,6 +48,7 @@ __device__ __forceinline__ PhiloxBlock philox4x32_10(uint32_t c0, uint32_t c1, u
 
 constexpr uint32_t kRngDomainParticle = 0u;  // Philox key word 1
 constexpr uint32_t kRngDomainCell = 1u;      // per-cell streams of the source's stochastic rounding
+constexpr uint32_t kRngDomainComb = 2u;      // the census comb's one offset per cell and cycle (jb_kernel_comb.hpp)
 
 __device__ __forceinline__ uint64_t rng_seed_state(uint32_t seed, uint32_t domain, uint64_t id) {
   const PhiloxBlock b = philox4x32_10(0u, 0u, (uint32_t)id, (uint32_t)(id >> 32), seed, domain);

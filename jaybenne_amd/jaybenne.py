@@ -256,6 +256,12 @@ class MeshData:
         self.ledger_history: list = []
         self._ledger_e0: Optional[float] = None     # e_census the next cycle starts from
         self._ledger_handoff = None                 # a transport for jb_ledger_reduce where the hand-off has none
+        # census comb (CombCensus; include/jaybenne_amd.h: jb_comb_census_plan): a cell that ends a cycle with more
+        # than comb_trigger photons comes out with comb_target; 0 = off (the reference: no population control)
+        self.comb_target = 0
+        self.comb_trigger = 0
+        self.comb_history: list = []                # one dict per cycle whose comb changed the swarm
+        self._comb_sorted = False                   # the last plan sorted the swarm
         self._make_mesh_handle(owner)
 
     def reserve(self, nslots: int) -> None:
@@ -629,6 +635,58 @@ def DefragParticles(md: MeshData) -> TaskStatus:
     return TaskStatus.complete
 
 
+def comb_trigger_of(target: int, trigger: float) -> int:
+    """``T = ceil(trigger * K)`` of the deck keys ``census_per_cell_max = K`` and ``census_comb_trigger`` (every host
+    forms it this way)."""
+    if target < 0:
+        raise ValueError("census_per_cell_max must be >= 0")
+    if not trigger >= 1.0:
+        raise ValueError("census_comb_trigger must be >= 1")
+    return int(np.ceil(trigger * target))
+
+
+def CombCensus(md: MeshData) -> Optional[dict]:
+    """Census population control at the end of a cycle (the reference has none): every cell that holds more than
+    ``md.comb_trigger`` ACTIVE photons comes out with exactly ``md.comb_target`` of equal weight, its energy kept
+    (include/jaybenne_amd.h: ``jb_comb_census_plan`` / ``_apply``).  The plan sorts the swarm by (block, cell).
+    Census photons live in owned blocks, so the comb is local to a rank; the new creation ids are dealt like the
+    source's: the ranks gather their counts, ``id_base = next_id + the counts of the lower ranks``, and ``next_id``
+    advances by the total on every rank.  Returns the cycle's record (also appended to ``md.comb_history``) when
+    the comb changed a swarm anywhere, else None."""
+    if md.comb_target <= 0:
+        return None
+    if md.replicated:
+        raise ValueError("the census comb needs the photons of a cell on one rank: not with a replicated mesh")
+    md._sync_stream()
+    plan = _lib.CombPlan()
+    _lib.check(md.lib.jb_comb_census_plan(md.pkg.ctx, md.handle, C.byref(md.sv), int(md.comb_trigger),
+                                          int(md.comb_target), int(md.cycle), C.byref(plan)))
+    md._comb_sorted = bool(plan.sorted)
+    new_ids = np.zeros(md.nranks, dtype=np.int64)
+    new_ids[md.rank] = int(plan.n_new_ids)
+    combed = np.zeros(md.nranks, dtype=np.int64)
+    combed[md.rank] = int(plan.cells_combed)
+    if md.comm is not None and md.nranks > 1:
+        both = md.comm.allreduce_sum_int64(np.concatenate([new_ids, combed]))
+        new_ids, combed = both[:md.nranks], both[md.nranks:]
+    rec = None
+    if plan.cells_combed > 0:
+        rep = _lib.CombReport()
+        id_base = md.next_id + int(new_ids[:md.rank].sum())
+        _lib.check(md.lib.jb_comb_census_apply(md.pkg.ctx, md.handle, C.byref(md.sv), id_base, C.byref(rep)))
+        rec = dict(cycle=md.cycle, n_before=int(plan.n_before), n_after=int(rep.n_after),
+                   n_new_ids=int(rep.n_new_ids), id_base=id_base, cells_combed=int(plan.cells_combed),
+                   max_per_cell=int(plan.max_per_cell), e_before=float(plan.e_before), e_after=float(rep.e_after))
+    elif int(combed.sum()) > 0:   # (another rank's swarm changed: the cycle is on record here too)
+        rec = dict(cycle=md.cycle, n_before=int(plan.n_before), n_after=int(plan.n_after), n_new_ids=0,
+                   id_base=md.next_id + int(new_ids[:md.rank].sum()), cells_combed=0,
+                   max_per_cell=int(plan.max_per_cell), e_before=float(plan.e_before), e_after=float(plan.e_before))
+    md.next_id += int(new_ids.sum())
+    if rec is not None:
+        md.comb_history.append(rec)
+    return rec
+
+
 def EstimateTimestepMesh(md: MeshData) -> float:
     """reference jaybenne.cpp:271-275"""
     return float(md.lib.jb_estimate_timestep(md.pkg.ctx))
@@ -797,7 +855,7 @@ def _radiation_step_ranks(md: MeshData, t_start: float, dt: float) -> TaskStatus
         led = _lib.EnergyLedger()
         _lib.check(md.lib.jb_ledger_last(pkg.ctx, C.byref(led)))
         md._ledger_record(led)
-    _defrag_after_step(md, int(rep.events))
+    _comb_and_defrag_after_step(md, int(rep.events))
     return TaskStatus.complete
 
 
@@ -889,14 +947,30 @@ def _radiation_step(md: MeshData, t_start: float, dt: float) -> TaskStatus:
             led.cycle = md.cycle
             md._ledger_reduce(led)
             md._ledger_record(led)
-        _defrag_after_step(md, int(after["n_events"] - before["n_events"]))
+        _comb_and_defrag_after_step(md, int(after["n_events"] - before["n_events"]))
     return TaskStatus.complete
 
 
-def _defrag_after_step(md: MeshData, events: int) -> None:
-    """DefragParticles at the end of a cycle: on the library's schedule (jb_defrag_policy) or every k-th cycle."""
+def _comb_and_defrag_after_step(md: MeshData, events: int) -> None:
+    """The end of a cycle: the census comb where it is on, then DefragParticles' schedule.  With the comb off this
+    is ``_defrag_after_step`` and nothing else."""
+    if md.comb_target <= 0:
+        _defrag_after_step(md, events)
+        return
+    CombCensus(md)
+    _defrag_after_step(md, events, sorted_by_comb=md._comb_sorted)
+
+
+def _defrag_after_step(md: MeshData, events: int, sorted_by_comb: bool = False) -> None:
+    """DefragParticles at the end of a cycle: on the library's schedule (jb_defrag_policy) or every k-th cycle.
+    ``sorted_by_comb``: the comb's plan has sorted the swarm in this cycle -- the k-th-cycle counter starts over;
+    the library's schedule has started over inside the plan (jb_comb_census_plan) and is still called: it reads
+    the cycle's kernel times and, one cycle behind a sort, never sorts."""
     pkg = md.pkg
     md._steps_since_defrag += 1
+    if sorted_by_comb and md.defrag_interval >= 0:
+        md._steps_since_defrag = 0
+        return
     if md.defrag_interval < 0:
         sorted_ = C.c_int32(0)
         if md.nranks == 1:

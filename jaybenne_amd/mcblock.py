@@ -299,6 +299,15 @@ class McblockDriver:
         # (not a parameter of the reference: DefragParticles -- here a sort of the swarm by cell, for
         # the locality of the cell gathers -- after every k-th cycle; 0 = never, as the reference)
         self.md.defrag_interval = pin.GetOrAddInteger("jaybenne", "defrag_interval", -1)
+        # (not parameters of the reference either: the census comb -- a cell that ends a cycle with more than
+        # ceil(census_comb_trigger * census_per_cell_max) photons comes out with census_per_cell_max; 0 = off)
+        target = pin.GetOrAddInteger("jaybenne_amd", "census_per_cell_max", 0)
+        trigger = pin.GetOrAddReal("jaybenne_amd", "census_comb_trigger", 2.0)
+        if target > 0 and replicated:
+            raise ValueError("census_per_cell_max: the census comb needs the photons of a cell on one rank; "
+                             "a replicated mesh spreads them over the ranks")
+        self.md.comb_target = target
+        self.md.comb_trigger = jb.comb_trigger_of(target, trigger)
         if ledger is None:
             ledger = pin.GetOrAddBoolean("jaybenne_amd", "ledger", False) or self.md.ledger_enabled()
         if bool(ledger) != self.md.ledger_enabled():
