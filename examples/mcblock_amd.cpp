@@ -581,6 +581,8 @@ int main(int argc, char **argv) {
     // ceil(census_comb_trigger * census_per_cell_max) photons comes out with census_per_cell_max; 0 = off)
     md.comb_target = pin.GetOrAddInteger("jaybenne_amd", "census_per_cell_max", 0);
     md.comb_trigger = jb::CombTrigger(md.comb_target, pin.GetOrAddReal("jaybenne_amd", "census_comb_trigger", 2.0));
+    // (as the Python driver: the order within a cell behind a sort -- any, or id: the canonical order)
+    jb::SetCellOrder(&md, jb::CellOrderOf(pin.GetOrAddString("jaybenne_amd", "cell_order", "any")));
     jb::InitializeRadiation(&md, initial_radiation == "thermal");
     // --ledger FILE (or <jaybenne_amd> ledger = true, or JB_LEDGER=1): the energy ledger of every cycle
     std::FILE *ledger_file = nullptr;

@@ -340,9 +340,30 @@ jb_status jb_remove_marked_particles(jb_context *ctx, jb_swarm_view *swarm);
  * position) -- the order photons are sourced in, which keeps the cell data a wave gathers in the L2
  * of its XCD and which diffusion loosens from cycle to cycle (all-DDMC 3-D, 1e8 photons: 26.5 ms per
  * cycle at cycle 2, 39.9 at cycle 16).  Nothing a particle carries changes; particles of one cell
- * come out in arbitrary order.  Works through 128 bytes of library scratch memory per particle.
- * Asynchronous on the context's stream. */
+ * come out in arbitrary order (JB_CELL_ORDER_ANY, the default; jb_set_cell_order below).  Works through 128 bytes
+ * of library scratch memory per particle.  Asynchronous on the context's stream. */
 jb_status jb_defrag_particles(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm);
+/* The order of the photons WITHIN a cell behind a sort.  JB_CELL_ORDER_ANY (the default): whatever order the waves
+ * of the sort's move reached the cell's counter in -- it differs from run to run.  JB_CELL_ORDER_BY_ID, the
+ * canonical order: jb_defrag_particles sorts the first swarm->n slots by the triple (sort key, id, input slot) --
+ * the sort key is (resident block, cell) as above, one past the last cell for every slot that is not an ACTIVE
+ * photon in a resident block; the id is compared as a full unsigned 64-bit word (bit 63 of a hole's id takes part).
+ * Live ids are unique, so the output does not depend on the input's slot order; the input slot only breaks ties
+ * among dead slots.  Nothing a photon carries changes, and a swarm already in this order is not moved at all: one
+ * pass over (key, id) decides that and finds the largest id and key, which set the number of radix passes (8-bit
+ * digits of the id, then of the key: 4 + 3 for 1e8 photons in 128^3 cells; ids with bit 63 set force all 8 of the
+ * id).  In this mode the call synchronises the stream ONCE, for that 16-byte read-back.  Same limits (2^32 - 1
+ * photons, 2^32 - 2 cells); scratch: 20 1/8 bytes per photon on top of the 128 (two 8-byte (word, slot) arrays,
+ * the 4-byte destinations, the digit counts); if it cannot be allocated the swarm is left as it was and JB_ERR_HIP
+ * is returned, as in the default mode.  No atomics on photons' data, no floating point: the same photons give the
+ * same slots, bit for bit, whatever order they came in.  jb_defrag_policy sorts this way too when the mode is on
+ * (and times the sort as S as before: a dearer sort is scheduled less often); so does jb_comb_census_plan.
+ * With the mode off no kernel of the canonical sort is launched and every call does what it did.
+ * JB_CELL_ORDER=id in the environment makes BY_ID the default of jb_initialize.  jb_set_cell_order: JB_ERR_INVALID
+ * for any other mode (the mode stays); changing the mode discards a plan of jb_comb_census_plan not yet applied. */
+enum { JB_CELL_ORDER_ANY = 0, JB_CELL_ORDER_BY_ID = 1 };
+jb_status jb_set_cell_order(jb_context *ctx, int mode);
+int jb_get_cell_order(const jb_context *ctx);
 /* The default schedule of DefragParticles ("defrag_interval = -1", what RadiationStep of the hosts
  * calls at the end of a cycle, after it has read the cycle's event count): the library times the
  * tracking kernels of every jb_transport_photons* call and every sort with HIP events on the
@@ -409,8 +430,18 @@ jb_status jb_release_scratch(jb_context *ctx);
  * sets swarm->n (n_after <= n_before: the call never needs capacity) and reports the census energy behind it,
  * summed in a fixed order; it synchronises too.  The plan lives in the library's scratch memory: no other call
  * that uses this context may come between the two.
- * Which photons of a cell survive depends on the order the sort left them in, which is arbitrary within a cell:
- * counts, energies per cell and the distribution do not differ from run to run, the surviving ids can.
+ * Which photons of a cell survive depends on the order the sort left them in.  JB_CELL_ORDER_ANY (the default): that
+ * order is arbitrary within a cell -- counts, energies per cell and the distribution do not differ from run to run,
+ * the surviving ids can.  JB_CELL_ORDER_BY_ID (jb_set_cell_order): the plan asks "in canonical order already?" and
+ * otherwise runs the canonical sort (sorted reports which), so the photons of a cell are combed in the order of
+ * their creation ids: the survivors, the weights and the id every further copy takes are then a function of the
+ * photons alone, not of their slots -- the same from run to run, whenever the swarm was last sorted and however
+ * the blocks are dealt to ranks.  To that end the running weights C_j are formed exactly in this mode -- 128-bit
+ * fixed-point sums on the scale of the cell's largest weight (weights below 2^-95 of it are truncated, negative ones
+ * count as zero), each rounded once -- because a floating-point sum tree aligned to the swarm's slots would round
+ * the same cell differently at another offset.  In the output of jb_comb_census_apply the survivors (first copies) are again in
+ * canonical order; a further copy sits right behind its original with an id above every old one, so the next
+ * canonical sort moves it behind the cell's older photons -- the same way in every run.
  * JB_ERR_INVALID: target_K < 1, target_K > trigger_T, trigger_T >= 2^32, epoch >= 2^20, the limits of
  * jb_defrag_particles (2^32 - 1 photons, 2^32 - 2 cells), apply without a plan for this swarm.  Scratch: what the
  * sort takes plus 16 bytes per photon; if it cannot be allocated, JB_ERR_HIP and the swarm is as it was. */
@@ -421,7 +452,8 @@ typedef struct jb_comb_plan {
   int64_t cells_combed;
   int64_t max_per_cell;  /* most ACTIVE photons in one cell, before the comb */
   double e_before;       /* weight of the ACTIVE photons, summed in a fixed order */
-  int64_t sorted;        /* 1: the plan sorted the swarm; 0: it was in (block, cell) order already */
+  int64_t sorted;        /* 1: the plan sorted the swarm; 0: it was in (block, cell) order -- under
+                          * JB_CELL_ORDER_BY_ID: in canonical order -- already */
 } jb_comb_plan;
 typedef struct jb_comb_report {
   int64_t n_after;

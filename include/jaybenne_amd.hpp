@@ -74,6 +74,7 @@ class StateDescriptor {
   int seed() const { return jb_param_seed(ctx_); }  // Param<int>("seed"), jaybenne.cpp:187-190
   // arithmetic of the gray IMC tracking step: JB_ARITH_LEAN (default) or JB_ARITH_EXACT
   void SetArithmetic(int mode) { Check(jb_set_arithmetic(ctx_, mode)); }
+  void SetCellOrder(int mode) { Check(jb_set_cell_order(ctx_, mode)); }
   int Arithmetic() const { return jb_get_arithmetic(ctx_); }
 
  private:
@@ -562,6 +563,17 @@ inline TaskStatus UpdateFluid(MeshData *md) { return Check(jb_update_fluid(md->c
 // the swarm sorted by block and cell, in place (jaybenne_amd.h: jb_defrag_particles)
 inline TaskStatus DefragParticles(MeshData *md) {
   return Check(jb_defrag_particles(md->ctx(), md->mesh(), &md->swarm));
+}
+// the order of the photons within a cell behind a sort: JB_CELL_ORDER_ANY (default) or JB_CELL_ORDER_BY_ID, the
+// canonical order by creation id (jaybenne_amd.h: jb_set_cell_order) -- DefragParticles, the library's schedule
+// and the comb's plan then sort by (block, cell, id)
+inline void SetCellOrder(MeshData *md, int mode) { Check(jb_set_cell_order(md->ctx(), mode)); }
+inline int GetCellOrder(MeshData *md) { return jb_get_cell_order(md->ctx()); }
+// the mode of the deck key <jaybenne_amd> cell_order = any | id
+inline int CellOrderOf(const std::string &value) {
+  if (value == "any") return JB_CELL_ORDER_ANY;
+  if (value == "id") return JB_CELL_ORDER_BY_ID;
+  throw std::invalid_argument("jaybenne_amd/cell_order = '" + value + "': one of any, id");
 }
 inline Real EstimateTimestepMesh(MeshData *md) { return jb_estimate_timestep(md->ctx()); }
 

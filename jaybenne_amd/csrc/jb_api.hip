@@ -25,6 +25,7 @@
 #include "jb_kernel_imc.hpp"
 #include "jb_kernel_ledger.hpp"
 #include "jb_kernel_comb.hpp"
+#include "jb_kernel_order.hpp"
 #include "jb_select.hpp"
 
 using namespace jb;
@@ -90,6 +91,8 @@ struct jb_context {
   // arithmetic of the gray IMC tracking step: lean (default) or exact (JB_EXACT_ARITH=1 in the
   // environment at jb_initialize, or jb_set_arithmetic)
   bool lean_arith = true;
+  // order of the photons within a cell behind a sort (JB_CELL_ORDER=id at jb_initialize, or jb_set_cell_order)
+  int cell_order = JB_CELL_ORDER_ANY;
   int blocks_per_cu_env = 0;  // JB_TRANSPORT_BLOCKS_PER_CU at jb_initialize (tuning aid), 0 = occupancy query
   bool no_ddmc_all = false;   // JB_NO_DDMC_ALL=1 at jb_initialize (tests: k_hybrid on all-DDMC meshes)
   int ddmc_lds_codes = 1;          // JB_DDMC_LDS_CODES=0: k_ddmc_q gathers the cell codes from device memory on any mesh (tests, A/B)
@@ -421,6 +424,7 @@ extern "C" jb_status jb_initialize(const jb_params *params, const jb_eos *eos,
     const char *ex = getenv("JB_EXACT_ARITH");
     ctx->lean_arith = !(ex && ex[0] == '1');
   }
+  if (const char *e = getenv("JB_CELL_ORDER")) ctx->cell_order = strcmp(e, "id") == 0 ? JB_CELL_ORDER_BY_ID : JB_CELL_ORDER_ANY;
   if (const char *e = getenv("JB_TRANSPORT_BLOCKS_PER_CU")) ctx->blocks_per_cu_env = atoi(e);
   if (const char *e = getenv("JB_NO_DDMC_ALL")) ctx->no_ddmc_all = e[0] == '1';
   if (const char *e = getenv("JB_NO_IMC_CELL")) ctx->no_imc_cell = e[0] == '1';
@@ -1359,6 +1363,16 @@ extern "C" jb_status jb_set_arithmetic(jb_context *ctx, int mode) {
 extern "C" int jb_get_arithmetic(const jb_context *ctx) {
   return ctx && ctx->lean_arith ? JB_ARITH_LEAN : JB_ARITH_EXACT;
 }
+extern "C" jb_status jb_set_cell_order(jb_context *ctx, int mode) {
+  if (!ctx || (mode != JB_CELL_ORDER_ANY && mode != JB_CELL_ORDER_BY_ID))
+    return fail(JB_ERR_INVALID, "jb_set_cell_order: mode = %d is neither JB_CELL_ORDER_ANY nor JB_CELL_ORDER_BY_ID", mode);
+  if (mode != ctx->cell_order) ctx->comb.valid = false;   // (the comb's arrays lie behind the sort's: a plan made before is none now)
+  ctx->cell_order = mode;
+  return JB_COMPLETE;
+}
+extern "C" int jb_get_cell_order(const jb_context *ctx) {
+  return ctx && ctx->cell_order == JB_CELL_ORDER_BY_ID ? JB_CELL_ORDER_BY_ID : JB_CELL_ORDER_ANY;
+}
 
 static jb_status fetch_counters(jb_context *ctx) {
   JB_HIP(hipMemcpyAsync(ctx->counters_h, ctx->counters_d, sizeof(unsigned long long) * kRankBase,
@@ -1535,9 +1549,61 @@ extern "C" jb_status jb_remove_marked_particles(jb_context *ctx, jb_swarm_view *
 }
 
 // scratch of the sort, in 8-byte words: the particle records (16 words each, on a 128-byte boundary), then
-// histogram / offsets (nbins), tile sums (ntiles) and keys (n), 4 bytes each
-static size_t sort_scratch_words(long long n, long long nbins, int ntiles) {
-  return (size_t)kSortRecWords * (size_t)n + (size_t)((nbins + ntiles + n) / 2 + 16);
+// histogram / offsets (nbins), tile sums (ntiles) and keys (n), 4 bytes each; under JB_CELL_ORDER_BY_ID the arrays
+// of the canonical sort behind them (jb_order_plan.hpp: order_layout)
+static size_t sort_scratch_words(const jb_context *ctx, long long n, long long nbins, int ntiles) {
+  const size_t words = (size_t)kSortRecWords * (size_t)n + (size_t)((nbins + ntiles + n) / 2 + 16);
+  return ctx->cell_order == JB_CELL_ORDER_BY_ID ? order_layout(n, words).end : words;
+}
+static OrderLayout sort_order_layout(long long n, long long nbins, int ntiles) {
+  return order_layout(n, (size_t)kSortRecWords * (size_t)n + (size_t)((nbins + ntiles + n) / 2 + 16));
+}
+
+// The canonical sort (jb_kernel_order.hpp): the first n slots by (sort key, id, input slot).  key: n words of
+// scratch for the sort keys (written here).  *moved = 0: the swarm was in that order already and nothing was
+// touched.  Synchronises the stream once, for the read-back of k_order_check.
+static jb_status order_sort(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, long long nbins, int ntiles,
+                            int *moved) {
+  *moved = 0;
+  const long long n = swarm->n;
+  const DevMesh &M = mesh->dm;
+  const unsigned nkeys = (unsigned)(nbins - 1);
+  const OrderLayout L = sort_order_layout(n, nbins, ntiles);
+  unsigned long long *base = (unsigned long long *)ctx->scratch_d;
+  unsigned long long *rec = base;
+  unsigned *key = (unsigned *)(base + (size_t)kSortRecWords * (size_t)n) + nbins + ntiles;
+  unsigned long long *pairs[2] = {base + L.pairs[0], base + L.pairs[1]};
+  unsigned *dest = (unsigned *)(base + L.dest), *cnt = (unsigned *)(base + L.cnt), *csum = (unsigned *)(base + L.csum);
+  OrderFlags *flags_d = (OrderFlags *)(base + L.flags);
+  const DevSwarm S = dev_swarm(swarm);
+  const int gn = grid_for(ctx, n);
+  OrderFlags flags{};
+  JB_HIP(hipMemsetAsync(flags_d, 0, sizeof(OrderFlags), ctx->stream));
+  hipLaunchKernelGGL(k_comb_keys, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, key);
+  hipLaunchKernelGGL(k_order_check, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)key, (const uint64_t *)S.id, n, flags_d);
+  JB_HIP(hipGetLastError());
+  JB_HIP(hipMemcpyAsync(&flags, flags_d, sizeof(OrderFlags), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  const OrderPlan plan = plan_order(n, flags.max_id, flags.max_key);
+  if (!flags.unsorted || plan.npasses == 0) return JB_COMPLETE;
+  const int tiles = (int)L.tiles, scan_tiles = (int)L.scan_tiles;
+  hipLaunchKernelGGL(k_order_init, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)key, (const uint64_t *)S.id, n,
+                     plan.pass[0].word, pairs[0]);
+  for (int q = 0; q < plan.npasses; ++q) {
+    const OrderPass &ps = plan.pass[q];
+    const unsigned long long *in = pairs[q & 1];
+    hipLaunchKernelGGL(k_order_count, dim3(tiles), dim3(kBlock), 0, ctx->stream, in, n, ps.shift, cnt, L.tiles);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(scan_tiles), dim3(kBlock), 0, ctx->stream, cnt, L.ncnt, csum);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, csum, scan_tiles);
+    hipLaunchKernelGGL(k_scan_add, dim3(scan_tiles), dim3(kBlock), 0, ctx->stream, cnt, L.ncnt, (const unsigned *)csum);
+    hipLaunchKernelGGL(k_order_scatter, dim3(tiles), dim3(kBlock), 0, ctx->stream, in, n, ps.shift, (const unsigned *)cnt,
+                       L.tiles, ps.next, (const unsigned *)key, (const uint64_t *)S.id, pairs[(q + 1) & 1], dest);
+  }
+  hipLaunchKernelGGL(k_order_pack, dim3(gn), dim3(kBlock), 0, ctx->stream, S, n, (const unsigned *)dest, rec);
+  hipLaunchKernelGGL(k_sort_unpack, dim3(gn), dim3(kBlock), 0, ctx->stream, S, n, (const unsigned long long *)rec);
+  JB_HIP(hipGetLastError());
+  *moved = 1;
+  return JB_COMPLETE;
 }
 
 extern "C" jb_status jb_defrag_particles(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm) {
@@ -1556,8 +1622,12 @@ extern "C" jb_status jb_defrag_particles(jb_context *ctx, jb_mesh *mesh, const j
   const long long nbins = (long long)nkeys + 1;                       // + the bin behind all cells
   const int ntiles = (int)((nbins + kScanTile - 1) / kScanTile);
   const size_t rec_words = (size_t)kSortRecWords * (size_t)n;
-  st = ensure_scratch(ctx, sort_scratch_words(n, nbins, ntiles), /*slack=*/false);
+  st = ensure_scratch(ctx, sort_scratch_words(ctx, n, nbins, ntiles), /*slack=*/false);
   if (st != JB_COMPLETE) return st;
+  if (ctx->cell_order == JB_CELL_ORDER_BY_ID) {
+    int moved = 0;
+    return order_sort(ctx, mesh, swarm, nbins, ntiles, &moved);
+  }
   unsigned long long *rec = (unsigned long long *)ctx->scratch_d;
   unsigned *hist = (unsigned *)(rec + rec_words);
   unsigned *sums = hist + nbins;
@@ -1594,7 +1664,7 @@ static CombScratch comb_scratch(const jb_context *ctx, long long n, long long nb
   c.ntiles = (int)((n + 1 + kScanTile - 1) / kScanTile);
   const size_t nt = (size_t)c.ntiles, half = (size_t)(n + 2) / 2;
   // offsets in 8-byte words from the start of the scratch memory (the sort's part: the layout of jb_defrag_particles)
-  size_t o = sort_scratch_words(n, nbins, sort_tiles);
+  size_t o = sort_scratch_words(ctx, n, nbins, sort_tiles);
   const size_t oC = o; o += (size_t)n;
   const size_t okcnt = o; o += half;
   const size_t oextra = o; o += half;
@@ -1672,18 +1742,30 @@ extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swar
   // In key order already (behind a DefragParticles, or a comb, that nothing has moved since)?  Then the sort's
   // move is left out -- and the order within a cell, which the move leaves to its atomics, stays the caller's:
   // the same sorted swarm then gives the same bits.
+  // Under JB_CELL_ORDER_BY_ID the test is "in canonical order already?", the sort is the canonical one (which makes
+  // that test itself), and the cells' ends come from the histogram and its scan either way.
+  const bool by_id = ctx->cell_order == JB_CELL_ORDER_BY_ID;
   unsigned unsorted = 0u;
-  unsigned *flag_d = (unsigned *)c.cpart;
-  JB_HIP(hipMemsetAsync(flag_d, 0, sizeof(unsigned), ctx->stream));
-  hipLaunchKernelGGL(k_comb_keys, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, c.key);
-  hipLaunchKernelGGL(k_comb_unsorted, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key, n, flag_d);
-  JB_HIP(hipGetLastError());
-  JB_HIP(hipMemcpyAsync(&unsorted, flag_d, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-  JB_HIP(hipStreamSynchronize(ctx->stream));
+  if (by_id) {
+    int moved = 0;
+    st = order_sort(ctx, mesh, swarm, nbins, (int)((nbins + kScanTile - 1) / kScanTile), &moved);
+    if (st != JB_COMPLETE) return st;
+    unsorted = moved ? 1u : 0u;
+  } else {
+    unsigned *flag_d = (unsigned *)c.cpart;
+    JB_HIP(hipMemsetAsync(flag_d, 0, sizeof(unsigned), ctx->stream));
+    hipLaunchKernelGGL(k_comb_keys, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, c.key);
+    hipLaunchKernelGGL(k_comb_unsorted, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key, n, flag_d);
+    JB_HIP(hipGetLastError());
+    JB_HIP(hipMemcpyAsync(&unsorted, flag_d, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    JB_HIP(hipStreamSynchronize(ctx->stream));
+  }
   const unsigned *ends = c.ends;
   if (unsorted) {
-    st = jb_defrag_particles(ctx, mesh, swarm);
-    if (st != JB_COMPLETE) return st;
+    if (!by_id) {
+      st = jb_defrag_particles(ctx, mesh, swarm);
+      if (st != JB_COMPLETE) return st;
+    }
     // the schedule of jb_defrag_policy starts over from a sorted swarm (as behind defrag_now; this sort is not
     // the one whose time the policy weighs against the kernels' loss)
     ctx->rate_ref = 0.0;
@@ -1691,8 +1773,9 @@ extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swar
     ctx->excess_ms = 0.0;
     ctx->cycles_since_sort = 0;
     out->sorted = 1;
-    hipLaunchKernelGGL(k_comb_keys, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, c.key);
-  } else {   // the histogram and its scan alone: the cells' starts, the ends one entry on
+    if (!by_id) hipLaunchKernelGGL(k_comb_keys, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, c.key);
+  }
+  if (by_id || !unsorted) {   // the histogram and its scan alone: the cells' starts, the ends one entry on
     const int sort_tiles = (int)((nbins + kScanTile - 1) / kScanTile);
     unsigned *hist = c.ends, *sums = hist + nbins;
     JB_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned) * (size_t)nbins, ctx->stream));
@@ -1702,11 +1785,26 @@ extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swar
     hipLaunchKernelGGL(k_scan_add, dim3(sort_tiles), dim3(kBlock), 0, ctx->stream, hist, nbins, (const unsigned *)sums);
     ends = hist + 1;
   }
-  hipLaunchKernelGGL(k_comb_seg_tiles, dim3(nt), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key,
-                     (const double *)S.w, n, c.C, c.tsum, c.tflag);
-  hipLaunchKernelGGL(k_comb_seg_sums, dim3(1), dim3(1024), 0, ctx->stream, c.tsum, (const unsigned *)c.tflag, nt);
-  hipLaunchKernelGGL(k_comb_seg_add, dim3(nt), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key, n, c.C,
-                     (const double *)c.tsum);
+  if (by_id) {
+    // exact running weights (jb_kernel_comb.hpp): 128-bit sums in the records' memory, which nothing uses before
+    // the move (2 n words, then 2 per tile: nt <= 7 n); the cells' scales where k_comb_decide's counts go later
+    U128 *C128 = (U128 *)c.rec, *tsum128 = C128 + n;
+    unsigned *cexp = c.kcnt;
+    JB_HIP(hipMemsetAsync(cexp, 0, sizeof(unsigned) * (size_t)(n + 1), ctx->stream));
+    hipLaunchKernelGGL(k_comb_cell_exp, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key,
+                       (const double *)S.w, ends, n, cexp);
+    hipLaunchKernelGGL(k_comb_xseg_tiles, dim3(nt), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key,
+                       (const double *)S.w, ends, (const unsigned *)cexp, n, C128, tsum128, c.tflag);
+    hipLaunchKernelGGL(k_comb_xseg_sums, dim3(1), dim3(1024), 0, ctx->stream, tsum128, (const unsigned *)c.tflag, nt);
+    hipLaunchKernelGGL(k_comb_xseg_add, dim3(nt), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key, ends,
+                       (const unsigned *)cexp, n, (const U128 *)C128, (const U128 *)tsum128, c.C);
+  } else {
+    hipLaunchKernelGGL(k_comb_seg_tiles, dim3(nt), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key,
+                       (const double *)S.w, n, c.C, c.tsum, c.tflag);
+    hipLaunchKernelGGL(k_comb_seg_sums, dim3(1), dim3(1024), 0, ctx->stream, c.tsum, (const unsigned *)c.tflag, nt);
+    hipLaunchKernelGGL(k_comb_seg_add, dim3(nt), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key, n, c.C,
+                       (const double *)c.tsum);
+  }
   hipLaunchKernelGGL(k_comb_decide, dim3(grid_for(ctx, n + 1)), dim3(kBlock), 0, ctx->stream, M, n, nkeys,
                      (const unsigned *)c.key, ends, (const double *)c.C, T, K, ctx->dp.key0, epoch,
                      c.kcnt, c.extra);
@@ -1742,7 +1840,7 @@ extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swar
   ctx->comb.T = T;
   ctx->comb.K = K;
   ctx->comb.gen = ctx->scratch_gen;
-  ctx->comb.ends_shift = unsorted ? 0 : 1;
+  ctx->comb.ends_shift = unsorted && !by_id ? 0 : 1;
   return JB_COMPLETE;
 }
 
@@ -1894,7 +1992,7 @@ extern "C" jb_status jb_defrag_policy(jb_context *ctx, jb_mesh *mesh, const jb_s
     const unsigned long long nbins0 = (unsigned long long)M0.nblocks * (unsigned long long)M0.ntot + 1ull;
     const unsigned long long ntiles0 = (nbins0 + kScanTile - 1) / kScanTile;
     if (swarm->n < (1ll << 32) && nbins0 < (1ull << 32)) {
-      const size_t words = (size_t)kSortRecWords * (size_t)swarm->n + (size_t)((nbins0 + ntiles0 + swarm->n) / 2 + 16);
+      const size_t words = sort_scratch_words(ctx, swarm->n, (long long)nbins0, (int)ntiles0);
       if (ensure_scratch(ctx, words, /*slack=*/false) != JB_COMPLETE) {
         fprintf(stderr, "jaybenne_amd: no room for the scratch records of DefragParticles (%s): the swarm stays unsorted\n", g_err);
         (void)hipGetLastError();
@@ -1922,7 +2020,7 @@ extern "C" jb_status jb_defrag_policy(jb_context *ctx, jb_mesh *mesh, const jb_s
       const unsigned long long nbins1 = (unsigned long long)M1.nblocks * (unsigned long long)M1.ntot + 1ull;
       const unsigned long long ntiles1 = (nbins1 + kScanTile - 1) / kScanTile;
       if (swarm->n < (1ll << 32) && nbins1 < (1ull << 32)) {
-        const size_t words = (size_t)kSortRecWords * (size_t)swarm->n + (size_t)((nbins1 + ntiles1 + swarm->n) / 2 + 16);
+        const size_t words = sort_scratch_words(ctx, swarm->n, (long long)nbins1, (int)ntiles1);
         if (ensure_scratch(ctx, words, /*slack=*/false) != JB_COMPLETE) {
           fprintf(stderr, "jaybenne_amd: no room for the scratch records of DefragParticles (%s): the swarm stays unsorted\n", g_err);
           (void)hipGetLastError();

@@ -15,6 +15,8 @@
 // k_comb_seg_tiles   segmented inclusive scan of w inside tiles of kScanTile slots      12 read, 8 written
 // k_comb_seg_sums    one workgroup: exclusive segmented scan of the tiles' (sum, flag)  -
 // k_comb_seg_add     adds a tile's carry to the slots that continue the segment before  12 read, <= 8 written
+//   (JB_CELL_ORDER_BY_ID: k_comb_cell_exp and k_comb_xseg_tiles / _sums / _add instead -- the same scan over exact
+//   128-bit fixed-point weights, each C_j rounded once: below)
 // k_comb_decide      k_j and max(k_j - 1, 0) per slot                                   ~20 read, 8 written
 //   (k_scan_tiles / _sums / _add of the sort turn both into output slots and id offsets: 2 x 16)
 // k_comb_cells       cells combed, largest cell (per-workgroup partials)                per cell
@@ -180,6 +182,206 @@ __global__ void __launch_bounds__(kBlock)
     if (base + q < n && key[base + q] == kprev) C[base + q] = add + C[base + q];
 }
 
+// ---- the running weights of the canonical order (JB_CELL_ORDER_BY_ID): exact, so that they are a function of the
+// cell's photons alone.  The sums above are trees aligned to absolute slots: the same cell at another offset in the
+// swarm (another rank count, other cells before it) gets other roundings.  Here every weight becomes a 128-bit
+// fixed-point number on a scale set by the largest weight of its cell (its mantissa at bits 42..94: 2^32 photons
+// fit below bit 127, weights 2^-95 of the largest and less are truncated), integer addition is associative, and
+// C_j is the one rounding of the exact prefix sum.  Negative weights count as zero; a cell with a weight that is
+// not finite gets C = inf and is left alone.
+struct U128 {
+  unsigned long long lo, hi;
+};
+__device__ __forceinline__ U128 u128_add(U128 a, U128 b) {
+  U128 r;
+  r.lo = a.lo + b.lo;
+  r.hi = a.hi + b.hi + (r.lo < a.lo ? 1ull : 0ull);
+  return r;
+}
+struct XSegPair {
+  U128 s;
+  unsigned f;
+};
+__device__ __forceinline__ XSegPair xseg_join(XSegPair a, XSegPair b) {
+  return XSegPair{b.f ? b.s : u128_add(a.s, b.s), a.f | b.f};
+}
+__device__ __forceinline__ XSegPair xseg_shfl_up(XSegPair v, int d) {
+  return XSegPair{U128{__shfl_up(v.s.lo, d, 64), __shfl_up(v.s.hi, d, 64)}, (unsigned)__shfl_up((int)v.f, d, 64)};
+}
+__device__ __forceinline__ XSegPair xseg_wave_scan(XSegPair mine, int lane, XSegPair &ex) {
+  XSegPair incl = mine;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const XSegPair up = xseg_shfl_up(incl, d);
+    if (lane >= d) incl = xseg_join(up, incl);
+  }
+  ex = xseg_shfl_up(incl, 1);
+  if (lane == 0) ex = XSegPair{U128{0ull, 0ull}, 0u};
+  return incl;
+}
+// the exponent field of a weight as the cell's scale sees it: 0 for a negative weight, 0x7ff for inf / nan
+__device__ __forceinline__ unsigned comb_wexp(double w) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(w);
+  const unsigned e = (unsigned)(b >> 52) & 0x7ffu;
+  if (e == 0x7ffu) return e;
+  return (b >> 63) ? 0u : e;
+}
+// w on the scale of a cell whose largest exponent field is emax
+__device__ __forceinline__ U128 comb_wfixed(double w, unsigned emax) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(w);
+  const unsigned e = (unsigned)(b >> 52) & 0x7ffu;
+  if ((b >> 63) || emax == 0x7ffu || e > emax) return U128{0ull, 0ull};
+  const unsigned long long mant = (b & 0xfffffffffffffull) | (e ? 0x10000000000000ull : 0ull);
+  const int sh = (int)(e ? e : 1u) - (int)(emax ? emax : 1u) + 42;   // <= 42
+  if (sh >= 0) return U128{mant << sh, sh ? mant >> (64 - sh) : 0ull};
+  return U128{-sh < 64 ? mant >> -sh : 0ull, 0ull};
+}
+__device__ __forceinline__ unsigned comb_start(const unsigned *ends, unsigned k) { return k > 0u ? ends[k - 1] : 0u; }
+
+// cexp[first slot of the cell] = the largest exponent field among the cell's weights (cexp zeroed before; integer
+// maxima: the same whatever their order; one atomic per wave where the wave lies within one cell)
+__global__ void __launch_bounds__(kBlock)
+    k_comb_cell_exp(const unsigned *key, const double *w, const unsigned *ends, long long n, unsigned *cexp) {
+  const int lane = threadIdx.x & 63;
+  const long long wave0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) - lane;
+  for (long long base = wave0; base < n; base += (long long)gridDim.x * blockDim.x) {
+    const long long s = base + lane;
+    const bool active = s < n;
+    const unsigned k = active ? key[s] : 0u;
+    unsigned e = active ? comb_wexp(w[s]) : 0u;
+    const unsigned k0 = (unsigned)__shfl((int)k, 0, 64);
+    const bool one_cell = __ballot(active && k != k0) == 0ull;
+    if (one_cell) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        const unsigned o = (unsigned)__shfl_down((int)e, off, 64);
+        e = o > e ? o : e;
+      }
+      if (lane == 0) atomicMax(&cexp[comb_start(ends, k0)], e);
+    } else if (active) {
+      atomicMax(&cexp[comb_start(ends, k)], e);
+    }
+  }
+}
+
+// k_comb_seg_tiles / _sums / _add over the fixed-point weights
+__global__ void __launch_bounds__(kBlock)
+    k_comb_xseg_tiles(const unsigned *key, const double *w, const unsigned *ends, const unsigned *cexp, long long n,
+                      U128 *C, U128 *tsum, unsigned *tflag) {
+  __shared__ U128 wave_s[kBlock / 64];
+  __shared__ unsigned wave_f[kBlock / 64];
+  const long long base = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
+  unsigned prev = (base > 0 && base - 1 < n) ? key[base - 1] : 0u;
+  unsigned emax = 0u;
+  U128 v[kScanItems], run{0ull, 0ull};
+  unsigned heads = 0u;
+#pragma unroll
+  for (int q = 0; q < kScanItems; ++q) {
+    const long long i = base + q;
+    bool head = true;
+    U128 wi{0ull, 0ull};
+    if (i < n) {
+      const unsigned k = key[i];
+      head = i == 0 || k != prev;
+      if (head || q == 0) emax = cexp[comb_start(ends, k)];
+      prev = k;
+      wi = comb_wfixed(w[i], emax);
+    }
+    run = head ? wi : u128_add(run, wi);
+    v[q] = run;
+    if (head) heads |= 1u << q;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  XSegPair ex;
+  const XSegPair incl = xseg_wave_scan(XSegPair{run, heads != 0u ? 1u : 0u}, lane, ex);
+  if (lane == 63) {
+    wave_s[wave] = incl.s;
+    wave_f[wave] = incl.f;
+  }
+  __syncthreads();
+  XSegPair before{U128{0ull, 0ull}, 0u}, total{U128{0ull, 0ull}, 0u};
+#pragma unroll
+  for (int q = 0; q < kBlock / 64; ++q) {
+    const XSegPair p{wave_s[q], wave_f[q]};
+    if (q < wave) before = xseg_join(before, p);
+    total = xseg_join(total, p);
+  }
+  const XSegPair open = xseg_join(before, ex);
+#pragma unroll
+  for (int q = 0; q < kScanItems; ++q) {
+    if (base + q >= n) break;
+    const bool continues = (heads & ((2u << q) - 1u)) == 0u;
+    C[base + q] = continues ? u128_add(open.s, v[q]) : v[q];
+  }
+  if (threadIdx.x == 0) {
+    tsum[blockIdx.x] = total.s;
+    tflag[blockIdx.x] = total.f;
+  }
+}
+__global__ void __launch_bounds__(1024) k_comb_xseg_sums(U128 *tsum, const unsigned *tflag, int count) {
+  __shared__ U128 wave_s[16];
+  __shared__ unsigned wave_f[16];
+  __shared__ U128 carry_s;
+  __shared__ unsigned carry_f;
+  if (threadIdx.x == 0) {
+    carry_s = U128{0ull, 0ull};
+    carry_f = 0u;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int s0 = 0; s0 < count; s0 += 1024) {
+    const int q = s0 + (int)threadIdx.x;
+    const XSegPair mine = q < count ? XSegPair{tsum[q], tflag[q]} : XSegPair{U128{0ull, 0ull}, 0u};
+    XSegPair ex;
+    const XSegPair incl = xseg_wave_scan(mine, lane, ex);
+    if (lane == 63) {
+      wave_s[wave] = incl.s;
+      wave_f[wave] = incl.f;
+    }
+    __syncthreads();
+    XSegPair before{U128{0ull, 0ull}, 0u}, total{U128{0ull, 0ull}, 0u};
+#pragma unroll
+    for (int p = 0; p < 16; ++p) {
+      const XSegPair t{wave_s[p], wave_f[p]};
+      if (p < wave) before = xseg_join(before, t);
+      total = xseg_join(total, t);
+    }
+    const XSegPair carry{carry_s, carry_f};
+    if (q < count) tsum[q] = xseg_join(carry, xseg_join(before, ex)).s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const XSegPair c = xseg_join(carry, total);
+      carry_s = c.s;
+      carry_f = c.f;
+    }
+    __syncthreads();
+  }
+}
+// adds the tile's carry where the slot continues the segment before the tile, and rounds every exact prefix sum
+// once: Cd[s] = C[s] * 2^(scale of the cell)
+__global__ void __launch_bounds__(kBlock)
+    k_comb_xseg_add(const unsigned *key, const unsigned *ends, const unsigned *cexp, long long n, const U128 *C,
+                    const U128 *tsum, double *Cd) {
+  const long long tile0 = (long long)blockIdx.x * kScanTile;
+  const bool first = blockIdx.x == 0;
+  const unsigned kprev = first ? 0u : key[tile0 - 1];
+  const U128 add = first ? U128{0ull, 0ull} : tsum[blockIdx.x];
+  const long long base = tile0 + (long long)threadIdx.x * kScanItems;
+#pragma unroll
+  for (int q = 0; q < kScanItems; ++q) {
+    const long long i = base + q;
+    if (i >= n) break;
+    const unsigned k = key[i];
+    U128 c = C[i];
+    if (!first && k == kprev) c = u128_add(add, c);
+    const unsigned emax = cexp[comb_start(ends, k)];
+    double d;
+    if (emax == 0x7ffu) d = __builtin_huge_val();
+    else d = ldexp((double)c.hi * 18446744073709551616.0 + (double)c.lo, (int)(emax ? emax : 1u) - 42 - 1075);
+    Cd[i] = d;
+  }
+}
+
 // The slots [start, end) of cell k of the sorted swarm (ends[k]: k_sort_pack leaves the histogram's offsets at the
 // END of every cell; behind the scan alone they are the cells' starts, and ends is that array from entry 1 on)
 // and whether the cell is combed: more than T photons, and a weight the rule can divide.
@@ -306,16 +508,7 @@ __global__ void __launch_bounds__(kBlock)
         double W;
         if (comb_cell(ends, C, k, T, start, end, W)) w = W / (double)K;
       }
-      v2u *o = (v2u *)&stage[wave][lane][0];
-      auto bits = [](double v) { return (u64)__double_as_longlong(v); };
-      o[0] = v2u{bits(S.x[s]), bits(S.y[s])};
-      o[1] = v2u{bits(S.z[s]), bits(S.vx[s])};
-      o[2] = v2u{bits(S.vy[s]), bits(S.vz[s])};
-      o[3] = v2u{bits(S.t[s]), bits(w)};
-      o[4] = v2u{bits(S.e[s]), (u64)S.id[s]};
-      o[5] = v2u{(u64)S.rng[s], (u64)(unsigned)S.ip[s] | ((u64)(unsigned)S.jp[s] << 32)};
-      o[6] = v2u{(u64)(unsigned)S.kp[s] | ((u64)(unsigned)S.blk[s] << 32), (u64)(unsigned)S.status[s]};
-      o[7] = v2u{0ull, 0ull};
+      sort_stage(&stage[wave][lane][0], S, s, w);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

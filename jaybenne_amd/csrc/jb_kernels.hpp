@@ -1713,10 +1713,48 @@ constexpr int kSortRecWords = 16;  // 8-byte words per record
 // its own record piece by piece -- eight instructions that each touch 64 different lines -- the
 // pieces of a line reached HBM separately: WRITE_SIZE 38.6 GB for 12.8 GB of records, 13.5 ms.)
 constexpr int kSortRowWords = 18;  // 16 words of record + 2 of padding per LDS row (bank spread)
+// The staging of the moves (k_sort_pack, k_order_pack, k_comb_pack): slot s as a record in the lane's LDS row,
+// with the weight w ...
+__device__ __forceinline__ void sort_stage(unsigned long long *row, const DevSwarm &S, long long s, double w) {
+  typedef unsigned long long u64;
+  typedef u64 v2u __attribute__((ext_vector_type(2)));
+  v2u *o = (v2u *)row;
+  auto bits = [](double v) { return (u64)__double_as_longlong(v); };
+  o[0] = v2u{bits(S.x[s]), bits(S.y[s])};
+  o[1] = v2u{bits(S.z[s]), bits(S.vx[s])};
+  o[2] = v2u{bits(S.vy[s]), bits(S.vz[s])};
+  o[3] = v2u{bits(S.t[s]), bits(w)};
+  o[4] = v2u{bits(S.e[s]), (u64)S.id[s]};
+  o[5] = v2u{(u64)S.rng[s], (u64)(unsigned)S.ip[s] | ((u64)(unsigned)S.jp[s] << 32)};
+  o[6] = v2u{(u64)(unsigned)S.kp[s] | ((u64)(unsigned)S.blk[s] << 32), (u64)(unsigned)S.status[s]};
+  o[7] = v2u{0ull, 0ull};
+}
+// ... and the wave's staged records of slots base .. base + 63 to rec[dest of the lane that staged them]
+__device__ __forceinline__ void sort_store_rows(unsigned long long (*rows)[kSortRowWords], int lane, long long base,
+                                                long long n, unsigned dest, unsigned long long *rec) {
+  typedef unsigned long long u64;
+  typedef u64 v2u __attribute__((ext_vector_type(2)));
+  // (LDS operations of one wave complete in order; the fence keeps the compiler from moving the
+  // reads of other lanes' rows above these writes)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const int piece = lane & 7;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = 8 * j + (lane >> 3);                     // the record these eight lanes store
+    const unsigned d = __shfl(dest, row, 64);
+    if (base + row < n) {
+      const v2u v = *(const v2u *)&rows[row][2 * piece];
+      *(v2u *)(rec + (size_t)kSortRecWords * (size_t)d + 2 * piece) = v;
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
 __global__ void __launch_bounds__(kBlock)
     k_sort_pack(DevSwarm S, long long n, const unsigned *key, unsigned *offs, unsigned long long *rec) {
   typedef unsigned long long u64;
-  typedef u64 v2u __attribute__((ext_vector_type(2)));
   __shared__ __attribute__((aligned(16))) u64 stage[kBlock / 64][64][kSortRowWords];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long wave0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) - lane;
@@ -1730,35 +1768,8 @@ __global__ void __launch_bounds__(kBlock)
     if (active && lane == head) first = atomicAdd(&offs[k], (unsigned)len);   // (one claim per run)
     first = __shfl(first, head, 64);
     const unsigned dest = first + (unsigned)(lane - head);
-    if (active) {
-      v2u *o = (v2u *)&stage[wave][lane][0];
-      auto bits = [](double v) { return (u64)__double_as_longlong(v); };
-      o[0] = v2u{bits(S.x[s]), bits(S.y[s])};
-      o[1] = v2u{bits(S.z[s]), bits(S.vx[s])};
-      o[2] = v2u{bits(S.vy[s]), bits(S.vz[s])};
-      o[3] = v2u{bits(S.t[s]), bits(S.w[s])};
-      o[4] = v2u{bits(S.e[s]), (u64)S.id[s]};
-      o[5] = v2u{(u64)S.rng[s], (u64)(unsigned)S.ip[s] | ((u64)(unsigned)S.jp[s] << 32)};
-      o[6] = v2u{(u64)(unsigned)S.kp[s] | ((u64)(unsigned)S.blk[s] << 32), (u64)(unsigned)S.status[s]};
-      o[7] = v2u{0ull, 0ull};
-    }
-    // (LDS operations of one wave complete in order; the fence keeps the compiler from moving the
-    // reads of other lanes' rows above these writes)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int piece = lane & 7;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int row = 8 * j + (lane >> 3);                     // the record these eight lanes store
-      const unsigned d = __shfl(dest, row, 64);
-      if (base + row < n) {
-        const v2u v = *(const v2u *)&stage[wave][row][2 * piece];
-        *(v2u *)(rec + (size_t)kSortRecWords * (size_t)d + 2 * piece) = v;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    if (active) sort_stage(&stage[wave][lane][0], S, s, S.w[s]);
+    sort_store_rows(stage[wave], lane, base, n, dest, rec);
   }
 }
 __global__ void __launch_bounds__(kBlock)

@@ -406,6 +406,18 @@ class MeshData:
     def ledger_enabled(self) -> bool:
         return self.lib.jb_ledger_enabled(self.pkg.ctx) == 1
 
+    # ---- the order of the photons within a cell behind a sort
+    @property
+    def cell_order(self) -> str:
+        """``"any"`` (the default) or ``"id"``: the canonical order -- DefragParticles, the library's schedule and
+        the census comb's plan sort by (block, cell, creation id), so that what a comb keeps does not depend on
+        the slots the photons came in (include/jaybenne_amd.h: ``jb_set_cell_order``)."""
+        return CELL_ORDERS[self.lib.jb_get_cell_order(self.pkg.ctx)]
+
+    @cell_order.setter
+    def cell_order(self, mode: str) -> None:
+        _lib.check(self.lib.jb_set_cell_order(self.pkg.ctx, cell_order_code(mode)))
+
     def _ledger_transport(self):
         """The jb_exchange_transport the ledgers of several ranks are gathered through."""
         if self.nranks == 1:
@@ -633,6 +645,17 @@ def DefragParticles(md: MeshData) -> TaskStatus:
     _lib.check(md.lib.jb_defrag_particles(md.pkg.ctx, md.handle, C.byref(md.sv)))
     md.defrags += 1
     return TaskStatus.complete
+
+
+CELL_ORDERS = ("any", "id")
+
+
+def cell_order_code(mode: str, key: str = "cell_order") -> int:
+    """``JB_CELL_ORDER_ANY`` / ``_BY_ID`` of ``any`` / ``id`` (the values of the deck key ``<jaybenne_amd> cell_order``);
+    anything else is an error that names ``key``."""
+    if mode not in CELL_ORDERS:
+        raise ValueError(f"{key} = {mode!r}: one of any, id")
+    return CELL_ORDERS.index(mode)
 
 
 def comb_trigger_of(target: int, trigger: float) -> int:

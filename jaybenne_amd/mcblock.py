@@ -248,6 +248,14 @@ def choose_decomposition(mesh: Mesh, cost: np.ndarray, nranks: int, device=None)
     return "replicated" if (small and unbalanced) else "blocks"
 
 
+def deck_cell_order(pin: ParameterInput) -> str:
+    """``<jaybenne_amd> cell_order = any | id`` (default ``any``); anything else raises with the key named."""
+    mode = pin.GetOrAddString("jaybenne_amd", "cell_order", "any").strip()
+    if mode not in ("any", "id"):
+        raise ValueError(f"jaybenne_amd/cell_order = {mode!r}: one of any, id")
+    return mode
+
+
 # ------------------------------------------------------------------------------------------------
 # device-side driver (needs the HIP library; imported lazily so that the host-only helpers above
 # stay usable without a GPU)
@@ -308,6 +316,10 @@ class McblockDriver:
                              "a replicated mesh spreads them over the ranks")
         self.md.comb_target = target
         self.md.comb_trigger = jb.comb_trigger_of(target, trigger)
+        # (nor this one: the order of the photons within a cell behind a sort -- any, or id: the canonical order)
+        order = deck_cell_order(pin)
+        if order != self.md.cell_order:
+            self.md.cell_order = order
         if ledger is None:
             ledger = pin.GetOrAddBoolean("jaybenne_amd", "ledger", False) or self.md.ledger_enabled()
         if bool(ledger) != self.md.ledger_enabled():
