@@ -583,6 +583,16 @@ int main(int argc, char **argv) {
     md.comb_trigger = jb::CombTrigger(md.comb_target, pin.GetOrAddReal("jaybenne_amd", "census_comb_trigger", 2.0));
     // (as the Python driver: the order within a cell behind a sort -- any, or id: the canonical order)
     jb::SetCellOrder(&md, jb::CellOrderOf(pin.GetOrAddString("jaybenne_amd", "cell_order", "any")));
+    // (as the Python driver: the boundary source -- a black wall of temperature bsource_<face>_temperature behind a
+    // domain face, bsource_num_particles photons per cycle over all such faces; every temperature 0 = off)
+    md.bsource_num_particles = pin.GetOrAddInteger("jaybenne_amd", "bsource_num_particles", 0);
+    {
+      static const char *const kFaces[6] = {"ix1", "ox1", "ix2", "ox2", "ix3", "ox3"};
+      for (int f = 0; f < 6; ++f) {
+        const double temp = pin.GetOrAddReal("jaybenne_amd", std::string("bsource_") + kFaces[f] + "_temperature", 0.0);
+        if (temp != 0.0) jb::SetBoundarySource(&md, f, temp);
+      }
+    }
     jb::InitializeRadiation(&md, initial_radiation == "thermal");
     // --ledger FILE (or <jaybenne_amd> ledger = true, or JB_LEDGER=1): the energy ledger of every cycle
     std::FILE *ledger_file = nullptr;
@@ -615,7 +625,11 @@ int main(int argc, char **argv) {
                   (long long)md.swarm.n, (long long)md.events);
       if (jb::LedgerEnabled(&md)) {
         const jb::EnergyLedger &l = md.ledger;
-        if (ledger_file) std::fprintf(ledger_file, "%s\n", jb::LedgerJson(l).c_str());
+        const bool sourced_faces = !md.boundary_source_history.empty() &&
+                                   md.boundary_source_history.back().cycle == (int64_t)md.cycle;
+        if (ledger_file)
+          std::fprintf(ledger_file, "%s\n", (sourced_faces ? jb::LedgerJson(l, md.boundary_source_history.back())
+                                                           : jb::LedgerJson(l)).c_str());
         std::printf(" leak=[%.6e, %.6e, %.6e, %.6e, %.6e, %.6e] residual=%.3e", l.e_escaped[0], l.e_escaped[1],
                     l.e_escaped[2], l.e_escaped[3], l.e_escaped[4], l.e_escaped[5], l.residual);
       }

@@ -212,6 +212,76 @@ jb_status jb_source_photons_fill_range(jb_context *ctx, jb_mesh *mesh, const jb_
                                        const int64_t *slot_base_host, const uint64_t *id_base_host,
                                        const int32_t *first_in_block_host, int set_energy_delta);
 
+/* ---- boundary source: Planckian inflow through chosen domain faces (the reference has none: its sources are
+ * inside the volume, sourcing.cpp).  Off by default; with every face off no kernel of it is launched and every
+ * call above and below takes the branches it took and gives the bits it gave.  DESIGN.md 4.8.
+ *
+ * Which faces.  A boundary source is a temperature T_f > 0 on a domain face f; faces are numbered 0..5 = ix1, ox1,
+ *   ix2, ox2, ix3, ox3.  T_f = 0: the face is off.  Only faces of active axes (f < 2 ndim) whose swarm boundary is
+ *   not periodic may be set; both are checked where the mesh is known, by jb_source_boundary_count.
+ * Which cells, how much energy.  A SOURCE FACE CELL is an interior cell of an owned block whose face f lies on the
+ *   domain boundary.  Per cycle each emits E_c = sb T_f^4 A_c dt -- with a c / 4 = sb the one-sided flux of a black
+ *   wall --, A_c the area of the cell's face from the block's own widths (on an inactive axis the width is the
+ *   full extent, as blk_dx holds it), sb = jb_opacity.sb; evaluated as ((sb (T^2 T^2)) A) dt.
+ * How many photons.  num_particles = N_b are asked for over all source faces of the WHOLE mesh; npc = N_b /
+ *   face_cells_total, the host passing the global number of source face cells (jb_boundary_face_cells, summed over
+ *   the ranks), so that nothing depends on the decomposition.  npc < 1: JB_ERR_INVALID.  A cell gets
+ *   snpc = floor(npc) + (npc - floor(npc) > xi) photons, xi the first draw of rng_seed_state(seed, domain 3 + f,
+ *   cell_stream_id(epoch, global block, cell)) -- cell and epoch as in the emission source --, each of weight
+ *   E_c / snpc: the energy sourced through a face is sb T_f^4 (face area) dt to rounding, every cycle.
+ * A photon's attributes come from its own stream, rng_stream_start(seed, id); with d = f / 2 the face's axis, ten
+ *   draws: (1) the position on axis (d + 1) % 3 as xc + dx (xi - 0.5), (2) on axis (d + 2) % 3 the same way
+ *   (inactive axes included, as the volume source does), (3, 4) sample_face_iso_dir(+c on a lower face, -c on an
+ *   upper one): the principal component on axis d, the other two on (d + 1) % 3 and (d + 2) % 3 -- the cyclic
+ *   assignment of ptcl_ddmc_albedo, transport_utils.hpp:280-397 --, (5-9) sample_planck_energy(sb, T_f),
+ *   (10) t = t_start + xi dt.  The coordinate on axis d is face + eps_imc dx_d on a lower face, face - eps_imc dx_d
+ *   on an upper one (face = xc -+ dx_d / 2 of the face cell): where the reference leaves a photon that has just
+ *   crossed that face (transport_utils.hpp:151-159), so an IMC cell tracks it and a DDMC cell's albedo admits or
+ *   reflects it.  ip / jp / kp the face cell, blk the block, status JB_ST_ACTIVE.
+ * Ids and slots.  Within a cycle block b has n_em[b] emission and n_bs[b] boundary photons and takes
+ *   n_em[b] + n_bs[b] consecutive ids from the per-block plan of the hosts (jaybenne_amd.hpp: PlanSource /
+ *   PlanSourceWithBoundary), the emission photons first, the boundary photons behind them ordered by face, then by
+ *   cell in (k, j, i) order, then by copy.  The boundary photons occupy the slots behind all emission photons of
+ *   the call.  Ids therefore do not depend on the partition.
+ *
+ *   jb_set_boundary_source / _get_: T_f of one face.  JB_ERR_INVALID: face outside 0..5, negative or non-finite T.
+ *   jb_set_boundary_source_count: N_b and the global number of source face cells for the STEP calls
+ *     (jb_radiation_step, jb_radiation_step_ranks: they run the boundary source behind the emission source when a
+ *     face is on; the same values on every rank).
+ *   jb_boundary_face_cells: the source face cells of this rank's owned blocks under the faces now set.
+ *   jb_boundary_prefix_words: int32 words of the prefix workspace of the two calls below for this mesh; prefix_dev
+ *     = NULL in both: a workspace of the library's own (one per context, as the step calls use it).
+ *   _count: per source face cell snpc; per resident block the number of new photons (plan_out->nper_block, host
+ *     [nblocks], the caller's) and the exclusive prefix over the block's (face, cell) entries (device); e_face /
+ *     n_face: energy and photons per face for this rank, summed in a fixed order without floating-point atomics
+ *     (the same call gives the same bits).  One synchronisation.  Every face off: zeros, no kernel.
+ *   _fill: the attributes of the new photons; block b writes slots slot_base[b].. and ids id_base[b]..
+ *   jb_boundary_source_last: e_face / n_face of the last _count on this context (this rank's; the hosts reduce
+ *     them over the ranks) and the number of boundary-source kernels launched since jb_initialize. */
+typedef struct jb_boundary_source_plan {
+  int32_t *nper_block;   /* host [nblocks], provided by the caller */
+  double e_face[6];
+  int64_t n_face[6];
+} jb_boundary_source_plan;
+typedef struct jb_boundary_source_record {
+  double e_face[6];
+  int64_t n_face[6];
+  int64_t kernel_launches;
+} jb_boundary_source_record;
+jb_status jb_set_boundary_source(jb_context *ctx, int face, double temperature);
+jb_status jb_get_boundary_source(const jb_context *ctx, int face, double *temperature);
+int jb_boundary_source_enabled(const jb_context *ctx);
+jb_status jb_set_boundary_source_count(jb_context *ctx, int64_t num_particles, int64_t face_cells_total);
+int64_t jb_boundary_face_cells(const jb_context *ctx, const jb_mesh *mesh);
+int64_t jb_boundary_prefix_words(const jb_mesh *mesh);
+jb_status jb_source_boundary_count(jb_context *ctx, jb_mesh *mesh, double dt, int64_t face_cells_total,
+                                   int64_t num_particles, uint32_t epoch, jb_boundary_source_plan *plan_out,
+                                   int32_t *prefix_dev);
+jb_status jb_source_boundary_fill(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, double t_start,
+                                  double dt, const int32_t *nper_block_host, const int32_t *prefix_dev,
+                                  const int64_t *slot_base_host, const uint64_t *id_base_host);
+jb_status jb_boundary_source_last(const jb_context *ctx, jb_boundary_source_record *out);
+
 /* TransportPhotons / TransportPhotons_DDMC(md, t_start, dt) -- jaybenne.hpp:59-60,
  * transport.cpp:28-181, transport_ddmc.cpp:28-237.  Particles [first,last) with status ACTIVE
  * are followed until census, absorption, escape, or until they enter a block that is not
@@ -548,7 +618,10 @@ double jb_estimate_timestep(const jb_context *ctx);
  * (Changed in round 4: the counter used to be a source-call counter incremented AFTER the source; a
  * caller that still passes 1 for the first cycle gets epoch 2 and different -- equally valid -- rounding
  * streams than the other hosts.  JB_ERR_INVALID for *cycle >= 2^19 - 1: beyond that the keys of the
- * emission and the in-cycle thermal source, (1 << 19) | cycle, would meet.) */
+ * emission and the in-cycle thermal source, (1 << 19) | cycle, would meet.)
+ * With a boundary source face on (jb_set_boundary_source) the boundary source runs behind the emission source, with
+ * the N_b and face-cell count of jb_set_boundary_source_count and the library's own prefix workspace; the ledger's
+ * sourced sweep covers both. */
 jb_status jb_radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, double t_start,
                             double dt, uint64_t *next_id, uint32_t *cycle, int32_t *prefix_dev);
 
@@ -577,6 +650,9 @@ jb_status jb_radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm
  *     on every rank alike); neither tally nor fluid is then updated.
  * The library's other failures (a HIP error in a kernel, a failing collective) are local, as in the
  * task calls themselves.
+ * Boundary source (a face on, on every rank alike): its count and the reserve for its photons happen before the
+ * first collective, like the emission's; the all-gather keeps its shape and the per-block word carries
+ * n_em + n_bs; the fill follows the emission fill (PlanSourceWithBoundary of jaybenne_amd.hpp).
  * Checked first, with JB_ERR_INVALID and no collective: null pointers, rank outside [0, nranks) or not the
  * mesh view's rank, nranks below the owners of the view, transport missing when nranks > 1, and a view
  * with ONE owner under nranks > 1 -- a replicated mesh (every rank holds every block: jb_mesh_view cannot

@@ -98,6 +98,13 @@ struct EnergyLedger : jb_energy_ledger {
   double e_start = 0.0, residual = 0.0;
 };
 // one combed cycle (MeshData::comb_history; the keys of the Python host's md.comb_history)
+// one cycle of the boundary source (MeshData::boundary_source_history; the keys of the Python host's
+// md.boundary_source_history): energy and photons sourced through each domain face
+struct BoundarySourceCycle {
+  int64_t cycle;
+  double e_face[6];
+  int64_t n_face[6];
+};
 struct CombRecord {
   int64_t cycle, n_before, n_after, n_new_ids;
   uint64_t id_base;
@@ -169,6 +176,19 @@ class MeshData {
   // comb_trigger photons comes out with comb_target; 0 = off (the reference: no population control)
   int64_t comb_target = 0, comb_trigger = 0;
   std::vector<CombRecord> comb_history;   // one record per cycle whose comb changed the swarm
+  // boundary source (SetBoundarySource; jaybenne_amd.h: jb_source_boundary_count): N_b photons per cycle over all
+  // source faces of the WHOLE mesh, and the number of source face cells of the whole mesh (SetBoundarySource sets it
+  // for a rank that holds the whole mesh; a host with several ranks stores the sum of jb_boundary_face_cells)
+  int64_t bsource_num_particles = 0, bsource_face_cells_total = 0;
+  std::vector<BoundarySourceCycle> boundary_source_history;   // one record per cycle, this rank's part
+  // counted by SourcePhotons(emission), filled by SourceBoundaryPhotons
+  struct {
+    bool valid = false;
+    uint64_t cycle = 0;
+    std::vector<int32_t> nper;
+    std::vector<uint64_t> id_base;
+    jb_boundary_source_plan plan{};
+  } bsource_pending;
 
  private:
   std::shared_ptr<StateDescriptor> pkg_;
@@ -202,6 +222,9 @@ struct SourcePlan {
   std::vector<uint64_t> id_base;
   int64_t total_local = 0;
   uint64_t next_id = 0;
+  // PlanSourceWithBoundary: the same for the boundary photons of the call (empty otherwise)
+  std::vector<int64_t> slot_base_boundary;
+  std::vector<uint64_t> id_base_boundary;
 };
 inline SourcePlan PlanSource(const std::vector<int32_t> &nper_local, const std::vector<int32_t> &gid,
                              const std::vector<long long> &all_counts, uint64_t next_id,
@@ -219,6 +242,26 @@ inline SourcePlan PlanSource(const std::vector<int32_t> &nper_local, const std::
     pl.total_local += nper_local[b];
   }
   pl.next_id = next_id + run;
+  return pl;
+}
+// ... and with the boundary source on (jaybenne_amd.h: jb_source_boundary_count): block b takes
+// nper_emission[b] + nper_boundary[b] CONSECUTIVE ids, the emission photons first; all_counts[g] is the sum of
+// both for global block g.  In the swarm the boundary photons lie behind all emission photons of the call.
+// total_local counts both.
+inline SourcePlan PlanSourceWithBoundary(const std::vector<int32_t> &nper_emission, const std::vector<int32_t> &nper_boundary,
+                                         const std::vector<int32_t> &gid, const std::vector<long long> &all_counts,
+                                         uint64_t next_id, int64_t n_now) {
+  SourcePlan pl = PlanSource(nper_emission, gid, all_counts, next_id, n_now);
+  const size_t nb = nper_emission.size();
+  pl.slot_base_boundary.resize(nb);
+  pl.id_base_boundary.resize(nb);
+  int64_t run = 0;
+  for (size_t b = 0; b < nb; ++b) {
+    pl.slot_base_boundary[b] = n_now + pl.total_local + run;
+    pl.id_base_boundary[b] = pl.id_base[b] + (uint64_t)nper_emission[b];
+    run += nper_boundary[b];
+  }
+  pl.total_local += run;
   return pl;
 }
 // The key of the per-cell rounding streams (`epoch` of jb_source_photons_count) as a function of
@@ -512,8 +555,31 @@ inline TaskStatus UpdateDerivedTransportFields(MeshData *md, const Real dt) {
   return Check(jb_update_derived_transport_fields(md->ctx(), md->mesh(), dt));
 }
 
+// ---- boundary source: Planckian inflow through chosen domain faces (jaybenne_amd.h) -----------------
+inline bool BoundarySourceOn(MeshData *md) { return jb_boundary_source_enabled(md->ctx()) == 1; }
+// A black wall of temperature `temperature` behind domain face `face` (0..5 = ix1 .. ox3); 0 = off.  For a rank that
+// holds the whole mesh (the number of source face cells is taken from its view).
+inline void SetBoundarySource(MeshData *md, int face, const Real temperature) {
+  Check(jb_set_boundary_source(md->ctx(), face, temperature));
+  md->bsource_face_cells_total = jb_boundary_face_cells(md->ctx(), md->mesh());
+  Check(jb_set_boundary_source_count(md->ctx(), md->bsource_num_particles, md->bsource_face_cells_total));
+}
+// jb_source_boundary_count into md->bsource_pending (the library's own prefix workspace)
+inline void CountBoundaryPhotons(MeshData *md, const Real dt) {
+  auto &bp = md->bsource_pending;
+  bp.nper.assign((size_t)md->nblocks(), 0);
+  bp.plan = jb_boundary_source_plan{};
+  bp.plan.nper_block = bp.nper.data();
+  Check(jb_source_boundary_count(md->ctx(), md->mesh(), dt, md->bsource_face_cells_total, md->bsource_num_particles,
+                                 SourceEpoch(md->cycle, SourceType::emission), &bp.plan, nullptr));
+  bp.cycle = md->cycle;
+  bp.valid = true;
+}
+
 // SourcePhotons<T, ST>(md, t_start, dt): per_block = the MeshBlockData instantiation used at
-// initialisation (one call per block, sourcing.cpp:68-69)
+// initialisation (one call per block, sourcing.cpp:68-69).  The emission source with the boundary source on also
+// counts the boundary photons: block b's take the ids behind its emission photons (PlanSourceWithBoundary), and
+// SourceBoundaryPhotons fills them.
 inline TaskStatus SourcePhotons(MeshData *md, SourceType st, const Real t_start, const Real dt,
                                 bool per_block = false) {
   const jb_params &p = md->pkg().params();
@@ -525,16 +591,52 @@ inline TaskStatus SourcePhotons(MeshData *md, SourceType st, const Real t_start,
   std::vector<int32_t> nper(nb, 0);
   Check(jb_source_photons_count(md->ctx(), md->mesh(), type, dt, per_block ? 1 : nb,
                                 SourceEpoch(md->cycle, st), nper.data(), md->prefix_dev()));
+  const bool with_boundary = st == SourceType::emission && BoundarySourceOn(md);
+  if (with_boundary) CountBoundaryPhotons(md, dt);
   // (this rank holds the whole mesh: global id = local index, global counts = local counts)
   std::vector<int32_t> gid(nb);
   std::vector<long long> all(nb);
-  for (int b = 0; b < nb; ++b) { gid[b] = b; all[b] = nper[b]; }
-  const SourcePlan pl = PlanSource(nper, gid, all, md->next_id, md->swarm.n);
+  for (int b = 0; b < nb; ++b) { gid[b] = b; all[b] = nper[b] + (with_boundary ? md->bsource_pending.nper[b] : 0); }
+  const SourcePlan pl = with_boundary
+      ? PlanSourceWithBoundary(nper, md->bsource_pending.nper, gid, all, md->next_id, md->swarm.n)
+      : PlanSource(nper, gid, all, md->next_id, md->swarm.n);
   md->Reserve(md->swarm.n + pl.total_local);
   Check(jb_source_photons_fill(md->ctx(), md->mesh(), &md->swarm, type, t_start, dt, nper.data(),
                                md->prefix_dev(), pl.slot_base.data(), pl.id_base.data()));
-  md->swarm.n += pl.total_local;
+  for (int b = 0; b < nb; ++b) md->swarm.n += nper[b];
   md->next_id = pl.next_id;
+  if (with_boundary) md->bsource_pending.id_base = pl.id_base_boundary;
+  return TaskStatus::complete;
+}
+
+// The boundary source of one cycle, right behind SourcePhotons(emission): every source face cell emits
+// sb T_f^4 A dt (jaybenne_amd.h).  Appends the cycle's record to md->boundary_source_history.  Every face off:
+// nothing, and no kernel.
+inline TaskStatus SourceBoundaryPhotons(MeshData *md, const Real t_start, const Real dt) {
+  if (!BoundarySourceOn(md)) return TaskStatus::complete;
+  auto &bp = md->bsource_pending;
+  const int nb = md->nblocks();
+  if (!bp.valid || bp.cycle != md->cycle) {   // (no emission source in front: the boundary photons alone)
+    CountBoundaryPhotons(md, dt);
+    std::vector<int32_t> gid(nb);
+    std::vector<long long> all(nb);
+    for (int b = 0; b < nb; ++b) { gid[b] = b; all[b] = bp.nper[b]; }
+    const SourcePlan pl = PlanSource(bp.nper, gid, all, md->next_id, md->swarm.n);
+    bp.id_base = pl.id_base;
+    md->next_id = pl.next_id;
+  }
+  std::vector<int64_t> slot(nb);
+  int64_t tot = 0;
+  for (int b = 0; b < nb; ++b) { slot[b] = md->swarm.n + tot; tot += bp.nper[b]; }
+  md->Reserve(md->swarm.n + tot);
+  Check(jb_source_boundary_fill(md->ctx(), md->mesh(), &md->swarm, t_start, dt, bp.nper.data(), nullptr, slot.data(),
+                                bp.id_base.data()));
+  md->swarm.n += tot;
+  BoundarySourceCycle rec{};
+  rec.cycle = (int64_t)md->cycle;
+  for (int f = 0; f < 6; ++f) { rec.e_face[f] = bp.plan.e_face[f]; rec.n_face[f] = bp.plan.n_face[f]; }
+  md->boundary_source_history.push_back(rec);
+  bp.valid = false;
   return TaskStatus::complete;
 }
 
@@ -680,6 +782,20 @@ inline std::string LedgerJson(const EnergyLedger &l) {
   return std::string(buf, n > 0 ? (size_t)n : 0);
 }
 
+// ... with the boundary source's per-face terms of the same cycle appended (`--ledger` lines gain them only when a
+// face is on)
+inline std::string LedgerJson(const EnergyLedger &l, const BoundarySourceCycle &b) {
+  std::string s = LedgerJson(l);
+  char buf[512];
+  const int n = std::snprintf(buf, sizeof buf, ", \"e_sourced_face\": [%.17g, %.17g, %.17g, %.17g, %.17g, %.17g], "
+                              "\"n_sourced_face\": [%lld, %lld, %lld, %lld, %lld, %lld]}",
+                              b.e_face[0], b.e_face[1], b.e_face[2], b.e_face[3], b.e_face[4], b.e_face[5],
+                              (long long)b.n_face[0], (long long)b.n_face[1], (long long)b.n_face[2],
+                              (long long)b.n_face[3], (long long)b.n_face[4], (long long)b.n_face[5]);
+  if (!s.empty() && s.back() == '}') s.pop_back();
+  return s + std::string(buf, n > 0 ? (size_t)n : 0);
+}
+
 // jaybenne::RadiationStep(pmesh, t_start, dt) for one rank -- jaybenne.cpp:68-151
 inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt) {
   TraceRange timestep("Jaybenne::Timestep");
@@ -690,6 +806,7 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt)
   UpdateDerivedTransportFields(md, dt);
   const int64_t n_before = md->swarm.n;
   SourcePhotons(md, SourceType::emission, t_start, dt);
+  SourceBoundaryPhotons(md, t_start, dt);
   if (ledger && md->swarm.n > n_before)
     Check(jb_ledger_accumulate(md->ctx(), md->mesh(), &md->swarm, n_before, md->swarm.n, JB_LEDGER_SOURCED));
   Check(jb_zero_energy_tally(md->ctx(), md->mesh()));
@@ -737,6 +854,8 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt,
   comm.reserve = &MeshData::ReserveTrampoline;
   const bool ledger = LedgerEnabled(md);   // (on on every rank or on none: the step reduces it with one more all-gather)
   if (ledger) LedgerBegin(md, t_start, tr, rank, nranks);
+  const bool boundary = BoundarySourceOn(md);   // (the same faces, N_b and global face-cell count on every rank)
+  if (boundary) Check(jb_set_boundary_source_count(md->ctx(), md->bsource_num_particles, md->bsource_face_cells_total));
   uint32_t cycle = (uint32_t)md->cycle;
   jb_step_report rep{};
   const jb_status st = jb_radiation_step_ranks(md->ctx(), md->mesh(), &md->swarm, t_start, dt, &md->next_id, &cycle,
@@ -745,6 +864,14 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt,
   md->last_step = rep;
   if (Check(st) != TaskStatus::complete) return TaskStatus::iterate;
   md->events += rep.events;
+  if (boundary) {   // (sourced inside the call, behind the emission source; this rank's part)
+    jb_boundary_source_record last{};
+    Check(jb_boundary_source_last(md->ctx(), &last));
+    BoundarySourceCycle rec{};
+    rec.cycle = (int64_t)md->cycle;
+    for (int f = 0; f < 6; ++f) { rec.e_face[f] = last.e_face[f]; rec.n_face[f] = last.n_face[f]; }
+    md->boundary_source_history.push_back(rec);
+  }
   if (ledger) {   // (closed and reduced over the ranks inside the call)
     jb_energy_ledger led{};
     Check(jb_ledger_last(md->ctx(), &led));

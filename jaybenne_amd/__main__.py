@@ -26,7 +26,11 @@ def ledger_json(led: dict) -> str:
     keys = ("cycle", "t_start", "dt", "e_start", "e_sourced", "n_sourced", "e_escaped", "n_escaped",
             "e_escaped_unclassified", "n_escaped_unclassified", "e_absorbed", "n_absorbed", "e_census", "n_census",
             "e_tally", "e_delta", "e_material", "residual")
-    return json.dumps({k: led[k] for k in keys})
+    out = {k: led[k] for k in keys}
+    for k in ("e_sourced_face", "n_sourced_face"):     # (only with a boundary source face on)
+        if k in led:
+            out[k] = led[k]
+    return json.dumps(out)
 
 
 def main(argv=None) -> int:
@@ -85,6 +89,9 @@ def main(argv=None) -> int:
                     f"histories/s={n0 / dt:.3e} events/s={(drv.md.events - e0) / dt:.3e}")
             if ledger_file is not None:
                 led = drv.md.ledger
+                bsh = drv.md.boundary_source_history
+                if bsh and bsh[-1]["cycle"] == drv.md.cycle:   # per-face sourced energy of the boundary source
+                    led = dict(led, e_sourced_face=bsh[-1]["e_face"], n_sourced_face=bsh[-1]["n_face"])
                 ledger_file.write(ledger_json(led) + "\n")
                 line += " leak=[" + ", ".join(f"{e:.6e}" for e in led["e_escaped"]) + f"] residual={led['residual']:.3e}"
             if drv.md.comb_history and drv.md.comb_history[-1]["cycle"] == drv.md.cycle:

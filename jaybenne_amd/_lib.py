@@ -201,6 +201,15 @@ class CombReport(C.Structure):
     _fields_ = [("n_after", C.c_int64), ("n_new_ids", C.c_int64), ("e_after", C.c_double)]
 
 
+# jb_boundary_source_plan / jb_boundary_source_record (include/jaybenne_amd.h): the boundary source
+class BoundarySourcePlan(C.Structure):
+    _fields_ = [("nper_block", C.c_void_p), ("e_face", C.c_double * 6), ("n_face", C.c_int64 * 6)]
+
+
+class BoundarySourceRecord(C.Structure):
+    _fields_ = [("e_face", C.c_double * 6), ("n_face", C.c_int64 * 6), ("kernel_launches", C.c_int64)]
+
+
 # every entry point include/jaybenne_amd.h declares: name -> (restype, argtypes)
 _vp, _i64, _f64, _int = C.c_void_p, C.c_int64, C.c_double, C.c_int
 PROTOTYPES = {
@@ -220,6 +229,15 @@ PROTOTYPES = {
                                       _vp, _vp]),
     "jb_source_photons_fill_range": (_int, [_vp, _vp, C.POINTER(SwarmView), _int, _f64, _f64, _vp, _vp,
                                             _vp, _vp, _vp, _int]),
+    "jb_set_boundary_source": (_int, [_vp, _int, _f64]),
+    "jb_get_boundary_source": (_int, [_vp, _int, C.POINTER(C.c_double)]),
+    "jb_boundary_source_enabled": (_int, [_vp]),
+    "jb_set_boundary_source_count": (_int, [_vp, _i64, _i64]),
+    "jb_boundary_face_cells": (_i64, [_vp, _vp]),
+    "jb_boundary_prefix_words": (_i64, [_vp]),
+    "jb_source_boundary_count": (_int, [_vp, _vp, _f64, _i64, _i64, C.c_uint32, C.POINTER(BoundarySourcePlan), _vp]),
+    "jb_source_boundary_fill": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64, _vp, _vp, _vp, _vp]),
+    "jb_boundary_source_last": (_int, [_vp, C.POINTER(BoundarySourceRecord)]),
     "jb_transport_photons": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64, _i64, _i64, _int]),
     "jb_transport_photons_ddmc": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64, _i64, _i64,
                                          _int]),

@@ -26,6 +26,7 @@
 #include "jb_kernel_ledger.hpp"
 #include "jb_kernel_comb.hpp"
 #include "jb_kernel_order.hpp"
+#include "jb_kernel_bsource.hpp"
 #include "jb_select.hpp"
 
 using namespace jb;
@@ -125,6 +126,14 @@ struct jb_context {
   size_t ledger_gather_words = 0;
   jb_energy_ledger ledger_last{};
   bool ledger_has_last = false;
+  // boundary source (jb_set_boundary_source; jb_kernel_bsource.hpp): off (every temperature 0) by default
+  double bs_temp[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  long long bs_num_particles = 0, bs_face_cells_total = 0;   // what the step calls ask for (jb_set_boundary_source_count)
+  int *bs_prefix_d = nullptr;          // the step calls' prefix workspace (a host that drives the tasks brings its own)
+  size_t bs_prefix_words = 0;
+  char *bs_out_d = nullptr;            // [nblocks] counts, [nblocks][6] photons and energy of the last count call
+  size_t bs_out_blocks = 0;
+  jb_boundary_source_record bs_last{};
 };
 constexpr int kLedgerHead = 64;   // words in front of the partial sums (LW_N of them used)
 constexpr int kLedgerWords = (int)(sizeof(jb_energy_ledger) / 8);
@@ -167,6 +176,8 @@ struct jb_mesh {
   std::vector<int32_t> gid_host;
   int nowned = 0;
   bool one_owner = true;
+  // [nblocks][6]: 1 = face f of this owned block lies on the domain boundary (the boundary source's face cells)
+  std::vector<uint8_t> bface_host;
 };
 
 __global__ void k_rcp_refined(double b, double *out) { *out = m_rcp_refined(b); }
@@ -524,6 +535,8 @@ extern "C" jb_status jb_finalize(jb_context *ctx) {
   if (ctx->step_gather_d) (void)hipFree(ctx->step_gather_d);
   if (ctx->ledger_d) (void)hipFree(ctx->ledger_d);
   if (ctx->ledger_gather_d) (void)hipFree(ctx->ledger_gather_d);
+  if (ctx->bs_prefix_d) (void)hipFree(ctx->bs_prefix_d);
+  if (ctx->bs_out_d) (void)hipFree(ctx->bs_out_d);
   for (hipEvent_t e : ctx->tev) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->sort_ev) if (e) (void)hipEventDestroy(e);
   delete ctx;
@@ -657,6 +670,14 @@ extern "C" jb_status jb_mesh_create(jb_context *ctx, const jb_mesh_view *v, jb_m
   m->gid_host.assign(v->gid, v->gid + v->nblocks);
   for (int b = 0; b < v->nblocks; ++b) m->nowned += (!v->owned || v->owned[b]) ? 1 : 0;
   for (int g = 1; g < v->nblocks_total; ++g) m->one_owner = m->one_owner && v->owner[g] == v->owner[0];
+  m->bface_host.assign(6 * (size_t)v->nblocks, 0);
+  for (int b = 0; b < v->nblocks; ++b)
+    for (int f = 0; f < 2 * v->ndim && (!v->owned || v->owned[b]); ++f) {   // (bsource_on_boundary, on the host)
+      const int d = f >> 1;
+      const double half = 0.5 * v->blk_dx[3 * b + d];
+      m->bface_host[6 * (size_t)b + f] =
+          (f & 1) ? v->blk_xmax[3 * b + d] > v->gmax[d] - half : v->blk_xmin[3 * b + d] < v->gmin[d] + half;
+    }
   jb_status st;
 #define UP(field, count)                                                         \
   if ((st = upload(m, v->field, (size_t)(count), &D.field)) != JB_COMPLETE) {     \
@@ -1025,6 +1046,202 @@ extern "C" jb_status jb_source_photons_fill_range(jb_context *ctx, jb_mesh *mesh
                        first_in_block_host ? (const long long *)(tab_d + 3 * M.nblocks) : (const long long *)nullptr,
                        total);
   JB_HIP(hipGetLastError());
+#ifdef JB_INVARIANTS
+  {  // (checked build) SWARM over the slots just filled
+    long long lo = swarm->capacity, hi = 0;
+    for (int b = 0; b < M.nblocks; ++b)
+      if (nper[b] > 0) {
+        lo = slot_base_host[b] < lo ? slot_base_host[b] : lo;
+        hi = slot_base_host[b] + nper[b] > hi ? slot_base_host[b] + nper[b] : hi;
+      }
+    st = inv_sweep(ctx, M, dev_swarm(swarm), lo, hi, t_start + dt, true);
+    if (st != JB_COMPLETE) return st;
+  }
+#endif
+  JB_HIP(hipStreamSynchronize(ctx->stream));  // tab lives on this stack frame
+  return JB_COMPLETE;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The boundary source (jb_kernel_bsource.hpp): Planckian inflow through the domain faces that carry a temperature.
+static bool bsource_on(const jb_context *ctx) {
+  for (int f = 0; f < 6; ++f)
+    if (ctx->bs_temp[f] > 0.0) return true;
+  return false;
+}
+
+extern "C" jb_status jb_set_boundary_source(jb_context *ctx, int face, double temperature) {
+  if (!ctx) return fail(JB_ERR_INVALID, "jb_set_boundary_source: null context");
+  if (face < 0 || face > 5) return fail(JB_ERR_INVALID, "jb_set_boundary_source: face %d outside 0..5", face);
+  if (!(temperature >= 0.0) || !std::isfinite(temperature))
+    return fail(JB_ERR_INVALID, "jb_set_boundary_source: the temperature of face %d must be finite and >= 0", face);
+  ctx->bs_temp[face] = temperature;
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_get_boundary_source(const jb_context *ctx, int face, double *temperature) {
+  if (!ctx || !temperature) return fail(JB_ERR_INVALID, "jb_get_boundary_source: null argument");
+  if (face < 0 || face > 5) return fail(JB_ERR_INVALID, "jb_get_boundary_source: face %d outside 0..5", face);
+  *temperature = ctx->bs_temp[face];
+  return JB_COMPLETE;
+}
+
+extern "C" int jb_boundary_source_enabled(const jb_context *ctx) { return ctx && bsource_on(ctx) ? 1 : 0; }
+
+extern "C" jb_status jb_set_boundary_source_count(jb_context *ctx, int64_t num_particles, int64_t face_cells_total) {
+  if (!ctx) return fail(JB_ERR_INVALID, "jb_set_boundary_source_count: null context");
+  if (num_particles < 0 || face_cells_total < 0)
+    return fail(JB_ERR_INVALID, "jb_set_boundary_source_count: negative count");
+  ctx->bs_num_particles = num_particles;
+  ctx->bs_face_cells_total = face_cells_total;
+  return JB_COMPLETE;
+}
+
+extern "C" int64_t jb_boundary_prefix_words(const jb_mesh *mesh) {
+  if (!mesh) return 0;
+  const DevMesh &M = mesh->dm;
+  return (int64_t)M.nblocks * (bsource_layout(M.nx, M.ncell).off[6] + 1);
+}
+
+extern "C" int64_t jb_boundary_face_cells(const jb_context *ctx, const jb_mesh *mesh) {
+  if (!ctx || !mesh) return 0;
+  const DevMesh &M = mesh->dm;
+  int64_t cells = 0;
+  for (int b = 0; b < M.nblocks; ++b)
+    for (int f = 0; f < 6; ++f)
+      if (ctx->bs_temp[f] > 0.0 && mesh->bface_host[6 * (size_t)b + f]) cells += M.ncell / M.nx[f >> 1];
+  return cells;
+}
+
+extern "C" jb_status jb_boundary_source_last(const jb_context *ctx, jb_boundary_source_record *out) {
+  if (!ctx || !out) return fail(JB_ERR_INVALID, "jb_boundary_source_last: null argument");
+  *out = ctx->bs_last;
+  return JB_COMPLETE;
+}
+
+// the library's own prefix workspace (prefix_dev == NULL; the step calls)
+static jb_status bsource_step_prefix(jb_context *ctx, const jb_mesh *mesh) {
+  const size_t words = (size_t)jb_boundary_prefix_words(mesh);
+  if (ctx->bs_prefix_words >= words) return JB_COMPLETE;
+  if (ctx->bs_prefix_d) (void)hipFree(ctx->bs_prefix_d);
+  ctx->bs_prefix_d = nullptr;
+  ctx->bs_prefix_words = 0;
+  JB_HIP(hipMalloc(&ctx->bs_prefix_d, words * sizeof(int)));
+  ctx->bs_prefix_words = words;
+  return JB_COMPLETE;
+}
+
+// the (block, face) results of the count kernel: [nblocks] int | pad to 8 | [nblocks][6] long long | [nblocks][6] double
+static size_t bsource_out_counts(size_t nblocks) { return (nblocks * sizeof(int) + 7) / 8 * 8; }
+
+extern "C" jb_status jb_source_boundary_count(jb_context *ctx, jb_mesh *mesh, double dt, int64_t face_cells_total,
+                                              int64_t num_particles, uint32_t epoch,
+                                              jb_boundary_source_plan *plan_out, int32_t *prefix_dev) {
+  JB_RANGE("Jaybenne::SourceBoundaryPhotons1");
+  if (!ctx || !mesh || !plan_out || !plan_out->nper_block)
+    return fail(JB_ERR_INVALID, "jb_source_boundary_count: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  const DevMesh &M = mesh->dm;
+  for (int b = 0; b < M.nblocks; ++b) plan_out->nper_block[b] = 0;
+  for (int f = 0; f < 6; ++f) { plan_out->e_face[f] = 0.0; plan_out->n_face[f] = 0; }
+  for (int f = 0; f < 6; ++f) { ctx->bs_last.e_face[f] = 0.0; ctx->bs_last.n_face[f] = 0; }
+  if (!bsource_on(ctx)) return JB_COMPLETE;   // every face off: no kernel
+  for (int f = 0; f < 6; ++f) {
+    if (!(ctx->bs_temp[f] > 0.0)) continue;
+    if (f >= 2 * M.ndim)
+      return fail(JB_ERR_INVALID, "boundary source on face %d: axis %d is not active on a %d-D mesh", f, f >> 1, M.ndim);
+    if (M.bc[f] == BC_PERIODIC)
+      return fail(JB_ERR_INVALID, "boundary source on face %d: its swarm boundary is periodic", f);
+  }
+  if (!prefix_dev) {   // the library's own workspace
+    const jb_status pst = bsource_step_prefix(ctx, mesh);
+    if (pst != JB_COMPLETE) return pst;
+    prefix_dev = ctx->bs_prefix_d;
+  }
+  if (epoch >= (1u << 20))  // cell_stream_id keeps the source-call counter in 20 bits
+    return fail(JB_ERR_INVALID, "more than 2^20 source calls: the per-cell rounding streams would repeat");
+  if (face_cells_total < 1) return fail(JB_ERR_INVALID, "boundary source: no source face cells (face_cells_total < 1)");
+  const double npc = (double)num_particles / (double)face_cells_total;
+  if (!(npc >= 1.0))
+    return fail(JB_ERR_INVALID, "boundary source: %lld photons for %lld source face cells -- fewer than one per cell",
+                (long long)num_particles, (long long)face_cells_total);
+  if (!(npc < 2.0e9)) return fail(JB_ERR_INVALID, "boundary source: more than 2e9 photons per source face cell");
+  const size_t nb = (size_t)M.nblocks;
+  if (ctx->bs_out_blocks < nb) {
+    if (ctx->bs_out_d) (void)hipFree(ctx->bs_out_d);
+    ctx->bs_out_d = nullptr;
+    ctx->bs_out_blocks = 0;
+    JB_HIP(hipMalloc(&ctx->bs_out_d, bsource_out_counts(nb) + nb * 6 * 16));
+    ctx->bs_out_blocks = nb;
+  }
+  int *nper_d = (int *)ctx->bs_out_d;
+  long long *n_bf_d = (long long *)(ctx->bs_out_d + bsource_out_counts(nb));
+  double *e_bf_d = (double *)(n_bf_d + 6 * nb);
+  BsFaces F;
+  for (int f = 0; f < 6; ++f) F.temp[f] = ctx->bs_temp[f];
+  const BsLayout L = bsource_layout(M.nx, M.ncell);
+  hipLaunchKernelGGL(k_bsource_count, dim3(M.nblocks), dim3(kBlock), 0, ctx->stream, M, ctx->dp, F, L, dt, npc, epoch,
+                     nper_d, (int *)prefix_dev, n_bf_d, e_bf_d);
+  JB_HIP(hipGetLastError());
+  ctx->bs_last.kernel_launches += 1;
+  std::vector<char> host(bsource_out_counts(nb) + nb * 6 * 16);
+  JB_HIP(hipMemcpyAsync(host.data(), ctx->bs_out_d, host.size(), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  const int *nper_h = (const int *)host.data();
+  const long long *n_bf = (const long long *)(host.data() + bsource_out_counts(nb));
+  const double *e_bf = (const double *)(n_bf + 6 * nb);
+  for (size_t b = 0; b < nb; ++b) {   // (blocks in resident order: a fixed order of additions)
+    plan_out->nper_block[b] = nper_h[b];
+    for (int f = 0; f < 6; ++f) {
+      plan_out->e_face[f] += e_bf[6 * b + f];
+      plan_out->n_face[f] += n_bf[6 * b + f];
+    }
+  }
+  for (int f = 0; f < 6; ++f) { ctx->bs_last.e_face[f] = plan_out->e_face[f]; ctx->bs_last.n_face[f] = plan_out->n_face[f]; }
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_source_boundary_fill(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
+                                             double t_start, double dt, const int32_t *nper_block_host,
+                                             const int32_t *prefix_dev, const int64_t *slot_base_host,
+                                             const uint64_t *id_base_host) {
+  JB_RANGE("Jaybenne::SourceBoundaryPhotons2");
+  if (!ctx || !mesh || !nper_block_host || !slot_base_host || !id_base_host)
+    return fail(JB_ERR_INVALID, "jb_source_boundary_fill: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  jb_status st = check_swarm(swarm, "jb_source_boundary_fill");
+  if (st != JB_COMPLETE) return st;
+  if (!bsource_on(ctx)) return JB_COMPLETE;
+  if (!prefix_dev) prefix_dev = ctx->bs_prefix_d;   // the library's own workspace, as the count call filled it
+  if (!prefix_dev) return fail(JB_ERR_INVALID, "jb_source_boundary_fill: no count call has filled the prefix workspace");
+  const DevMesh &M = mesh->dm;
+  st = ensure_scratch(ctx, (size_t)M.nblocks * 3 + 8);
+  if (st != JB_COMPLETE) return st;
+  const int32_t *nper = nper_block_host;
+  std::vector<long long> tab(3 * (size_t)M.nblocks);
+  long long total = 0;
+  for (int b = 0; b < M.nblocks; ++b) {
+    tab[b] = total;                                   // blk_first
+    tab[M.nblocks + b] = slot_base_host[b];           // slot_base
+    tab[2 * M.nblocks + b] = (long long)id_base_host[b];
+    if (nper[b] < 0) return fail(JB_ERR_INVALID, "negative particle count for block %d", b);
+    if (nper[b] > 0 && (slot_base_host[b] < 0 || slot_base_host[b] + nper[b] > swarm->capacity))
+      return fail(JB_ERR_CAPACITY, "swarm capacity %lld too small for block %d (slots %lld..%lld)",
+                  (long long)swarm->capacity, b, (long long)slot_base_host[b],
+                  (long long)slot_base_host[b] + nper[b]);
+    total += nper[b];
+  }
+  if (total == 0) return JB_COMPLETE;
+  long long *tab_d = ctx->scratch_d;
+  JB_HIP(hipMemcpyAsync(tab_d, tab.data(), sizeof(long long) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
+  BsFaces F;
+  for (int f = 0; f < 6; ++f) F.temp[f] = ctx->bs_temp[f];
+  const BsLayout L = bsource_layout(M.nx, M.ncell);
+  hipLaunchKernelGGL(k_bsource_fill, dim3(grid_for(ctx, total)), dim3(kBlock), 0, ctx->stream, M, ctx->dp,
+                     dev_swarm(swarm), F, L, t_start, dt, (const int *)prefix_dev, (const long long *)tab_d,
+                     (const long long *)(tab_d + M.nblocks), (const unsigned long long *)(tab_d + 2 * M.nblocks), total);
+  JB_HIP(hipGetLastError());
+  ctx->bs_last.kernel_launches += 1;
 #ifdef JB_INVARIANTS
   {  // (checked build) SWARM over the slots just filled
     long long lo = swarm->capacity, hi = 0;
@@ -2577,29 +2794,52 @@ static jb_status radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *s
   JB_RANGE("Jaybenne::Timestep");               // jaybenne.cpp:87 ... :145
   jb_status st = jb_update_derived_transport_fields(ctx, mesh, dt);
   if (st != JB_COMPLETE) return st;
-  if (ctx->params.do_emission) {
-    if (!prefix_dev) return fail(JB_ERR_INVALID, "emission source needs the prefix workspace");
-    std::vector<int32_t> nper(M.nblocks);
-    st = jb_source_photons_count(ctx, mesh, JB_SOURCE_EMISSION, dt, M.nblocks, *cycle, nper.data(),
-                                 prefix_dev);
-    if (st != JB_COMPLETE) return st;
-    std::vector<int64_t> slot(M.nblocks);
-    std::vector<uint64_t> ids(M.nblocks);
-    int64_t tot = 0;
+  const bool bs_on = bsource_on(ctx);
+  if (ctx->params.do_emission || bs_on) {
+    // Per block b: n_em[b] emission photons, then n_bs[b] boundary photons, take consecutive stream ids; in the
+    // swarm the boundary photons lie behind all emission photons of the call.  Both counts come first.
+    const int64_t n_before = swarm->n;
+    std::vector<int32_t> nper(M.nblocks, 0), nper_bs(M.nblocks, 0);
+    if (ctx->params.do_emission) {
+      if (!prefix_dev) return fail(JB_ERR_INVALID, "emission source needs the prefix workspace");
+      st = jb_source_photons_count(ctx, mesh, JB_SOURCE_EMISSION, dt, M.nblocks, *cycle, nper.data(),
+                                   prefix_dev);
+      if (st != JB_COMPLETE) return st;
+    }
+    if (bs_on) {
+      jb_boundary_source_plan bp{};
+      bp.nper_block = nper_bs.data();
+      st = jb_source_boundary_count(ctx, mesh, dt, ctx->bs_face_cells_total, ctx->bs_num_particles, *cycle, &bp,
+                                    nullptr);
+      if (st != JB_COMPLETE) return st;
+    }
+    std::vector<int64_t> slot(M.nblocks), slot_bs(M.nblocks);
+    std::vector<uint64_t> ids(M.nblocks), ids_bs(M.nblocks);
+    int64_t tot = 0, tot_bs = 0;
     for (int b = 0; b < M.nblocks; ++b) {
       slot[b] = swarm->n + tot;
-      ids[b] = *next_id + (uint64_t)tot;
+      ids[b] = *next_id + (uint64_t)(tot + tot_bs);
+      ids_bs[b] = ids[b] + (uint64_t)nper[b];
       tot += nper[b];
+      tot_bs += nper_bs[b];
     }
-    if (swarm->n + tot > swarm->capacity)
+    for (int64_t b = 0, run = 0; b < M.nblocks; ++b) { slot_bs[b] = swarm->n + tot + run; run += nper_bs[b]; }
+    if (swarm->n + tot + tot_bs > swarm->capacity)
       return fail(JB_ERR_CAPACITY, "swarm capacity %lld too small for %lld new particles",
-                  (long long)swarm->capacity, (long long)tot);
-    st = jb_source_photons_fill(ctx, mesh, swarm, JB_SOURCE_EMISSION, t_start, dt, nper.data(),
-                                prefix_dev, slot.data(), ids.data());
-    if (st != JB_COMPLETE) return st;
-    swarm->n += tot;
-    *next_id += (uint64_t)tot;
-    if (ctx->ledger_on && (st = ledger_sweep(ctx, M, dev_swarm(swarm), swarm->n - tot, swarm->n, LEDGER_SOURCED)) != JB_COMPLETE)
+                  (long long)swarm->capacity, (long long)(tot + tot_bs));
+    if (ctx->params.do_emission) {
+      st = jb_source_photons_fill(ctx, mesh, swarm, JB_SOURCE_EMISSION, t_start, dt, nper.data(),
+                                  prefix_dev, slot.data(), ids.data());
+      if (st != JB_COMPLETE) return st;
+    }
+    if (bs_on) {
+      st = jb_source_boundary_fill(ctx, mesh, swarm, t_start, dt, nper_bs.data(), ctx->bs_prefix_d, slot_bs.data(),
+                                   ids_bs.data());
+      if (st != JB_COMPLETE) return st;
+    }
+    swarm->n += tot + tot_bs;
+    *next_id += (uint64_t)(tot + tot_bs);
+    if (ctx->ledger_on && (st = ledger_sweep(ctx, M, dev_swarm(swarm), n_before, swarm->n, LEDGER_SOURCED)) != JB_COMPLETE)
       return st;
   }
   st = jb_zero_energy_tally(ctx, mesh);
@@ -2709,7 +2949,8 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
   JB_RANGE("Jaybenne::Timestep");               // jaybenne.cpp:87 ... :145
   const uint32_t epoch = *cycle + 1;             // (*cycle advances once every rank got this far)
   const size_t row = 1 + (size_t)M.nblocks_total;   // what a rank puts into the first all-gather
-  std::vector<int32_t> nper(M.nblocks, 0);
+  std::vector<int32_t> nper(M.nblocks, 0), nper_bs(M.nblocks, 0);
+  const bool bs_on = bsource_on(ctx);   // (the same faces on every rank, like the ledger)
   // this rank's part up to the first collective: a failure goes into the gathered status word
   auto local_part = [&]() -> jb_status {
     // the gather buffer first (without it this rank could not say anything: the one failure it cannot
@@ -2751,6 +2992,16 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
       for (int b = 0; b < M.nblocks; ++b) tot += nper[b];
       if ((st = step_reserve(comm, swarm, swarm->n + tot)) != JB_COMPLETE) return st;
     }
+    if (bs_on) {   // the boundary source's count and its room, like the emission's: before the collective
+      jb_boundary_source_plan bp{};
+      bp.nper_block = nper_bs.data();
+      st = jb_source_boundary_count(ctx, mesh, dt, ctx->bs_face_cells_total, ctx->bs_num_particles, epoch, &bp,
+                                    nullptr);
+      if (st != JB_COMPLETE) return st;
+      int64_t tot = 0;
+      for (int b = 0; b < M.nblocks; ++b) tot += (int64_t)nper[b] + nper_bs[b];
+      if ((st = step_reserve(comm, swarm, swarm->n + tot)) != JB_COMPLETE) return st;
+    }
     return JB_COMPLETE;
   };
   const jb_status local = local_part();
@@ -2760,7 +3011,8 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
   if (local != JB_COMPLETE) {
     mine[0] = (unsigned long long)(-(long long)local);
   } else {
-    for (int b = 0; b < M.nblocks; ++b) mine[1 + (size_t)mesh->gid_host[b]] = (unsigned long long)nper[b];
+    for (int b = 0; b < M.nblocks; ++b)   // (emission + boundary photons of the block: they take consecutive ids)
+      mine[1 + (size_t)mesh->gid_host[b]] = (unsigned long long)nper[b] + (unsigned long long)nper_bs[b];
   }
   if (multi) {
     unsigned long long *in_d = ctx->step_gather_d, *all_d = ctx->step_gather_d + row;
@@ -2781,14 +3033,22 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
   }
   *cycle = epoch;   // (keys the per-cell rounding streams of this cycle's emission source: SourceEpoch)
   jb_status st = JB_COMPLETE;
-  if (ctx->params.do_emission) {
+  if (ctx->params.do_emission || bs_on) {
     std::vector<long long> all_counts((size_t)M.nblocks_total, 0);
     for (int q = 0; q < nranks; ++q)
       for (size_t g = 0; g < (size_t)M.nblocks_total; ++g) all_counts[g] += (long long)all[(size_t)q * row + 1 + g];
-    const jaybenne_amd::SourcePlan pl = jaybenne_amd::PlanSource(nper, mesh->gid_host, all_counts, *next_id, swarm->n);
-    st = jb_source_photons_fill(ctx, mesh, swarm, JB_SOURCE_EMISSION, t_start, dt, nper.data(), prefix_dev,
-                                pl.slot_base.data(), pl.id_base.data());
-    if (st != JB_COMPLETE) return done(st);
+    jaybenne_amd::SourcePlan pl = jaybenne_amd::PlanSource(nper, mesh->gid_host, all_counts, *next_id, swarm->n);
+    if (bs_on) pl = jaybenne_amd::PlanSourceWithBoundary(nper, nper_bs, mesh->gid_host, all_counts, *next_id, swarm->n);
+    if (ctx->params.do_emission) {
+      st = jb_source_photons_fill(ctx, mesh, swarm, JB_SOURCE_EMISSION, t_start, dt, nper.data(), prefix_dev,
+                                  pl.slot_base.data(), pl.id_base.data());
+      if (st != JB_COMPLETE) return done(st);
+    }
+    if (bs_on) {
+      st = jb_source_boundary_fill(ctx, mesh, swarm, t_start, dt, nper_bs.data(), ctx->bs_prefix_d,
+                                   pl.slot_base_boundary.data(), pl.id_base_boundary.data());
+      if (st != JB_COMPLETE) return done(st);
+    }
     swarm->n += pl.total_local;
     *next_id = pl.next_id;
     if (ctx->ledger_on &&

@@ -49,6 +49,11 @@ __device__ __forceinline__ PhiloxBlock philox4x32_10(uint32_t c0, uint32_t c1, u
 constexpr uint32_t kRngDomainParticle = 0u;  // Philox key word 1
 constexpr uint32_t kRngDomainCell = 1u;      // per-cell streams of the source's stochastic rounding
 constexpr uint32_t kRngDomainComb = 2u;      // the census comb's one offset per cell and cycle (jb_kernel_comb.hpp)
+// the boundary source's stochastic rounding, one domain per domain face: 3 + f, f = 0..5 = ix1, ox1, ix2, ox2,
+// ix3, ox3 (jb_kernel_bsource.hpp)
+constexpr uint32_t kRngDomainBoundary = 3u;
+constexpr uint32_t kRngDomainBoundaryIx1 = 3u, kRngDomainBoundaryOx1 = 4u, kRngDomainBoundaryIx2 = 5u,
+                   kRngDomainBoundaryOx2 = 6u, kRngDomainBoundaryIx3 = 7u, kRngDomainBoundaryOx3 = 8u;
 
 __device__ __forceinline__ uint64_t rng_seed_state(uint32_t seed, uint32_t domain, uint64_t id) {
   const PhiloxBlock b = philox4x32_10(0u, 0u, (uint32_t)id, (uint32_t)(id >> 32), seed, domain);

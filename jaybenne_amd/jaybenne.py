@@ -262,6 +262,13 @@ class MeshData:
         self.comb_trigger = 0
         self.comb_history: list = []                # one dict per cycle whose comb changed the swarm
         self._comb_sorted = False                   # the last plan sorted the swarm
+        # boundary source (SetBoundarySource; include/jaybenne_amd.h: jb_source_boundary_count): Planckian inflow
+        # through the domain faces that carry a temperature; every face off (the default) = the reference
+        self.bsource_num_particles = 0              # N_b: photons per cycle over all source faces of the whole mesh
+        self.boundary_source_history: list = []     # one record per cycle: e_face / n_face summed over the ranks
+        self._bs_temp = [0.0] * 6
+        self._bs_prefix: Optional[torch.Tensor] = None
+        self._bs_plan = None                        # counted by SourcePhotons(emission), filled by SourceBoundaryPhotons
         self._make_mesh_handle(owner)
 
     def reserve(self, nslots: int) -> None:
@@ -533,6 +540,9 @@ def SourcePhotons(md: MeshData, source_type: SourceType, t_start: float, dt: flo
     _lib.check(md.lib.jb_source_photons_count(pkg.ctx, md.handle, int(source_type), dt,
                                               blocks_in_call, source_epoch(md.cycle, source_type),
                                               nper.ctypes.data, md.prefix.data_ptr()))
+    if source_type == SourceType.emission and boundary_source_on(md):
+        # the boundary photons of block b take the ids behind its emission photons: counted before the ids are dealt
+        return _source_emission_and_count_boundary(md, nper, t_start, dt)
     counts = _global_block_counts(md, nper)
     excl = np.concatenate(([0], np.cumsum(counts)[:-1]))
     id_base = np.ascontiguousarray(md.next_id + excl[md.resident_gids], dtype=np.uint64)
@@ -554,6 +564,129 @@ def SourcePhotons(md: MeshData, source_type: SourceType, t_start: float, dt: flo
     md.sv.n += tot
     md.next_id += int(counts.sum())
     return TaskStatus.complete
+
+
+# ---- boundary source: Planckian inflow through chosen domain faces (include/jaybenne_amd.h) ----------------
+FACE_NAMES = _lib.LEDGER_FACES      # ix1, ox1, ix2, ox2, ix3, ox3
+
+
+def SetBoundarySource(md: MeshData, face: int, temperature: float) -> None:
+    """A black wall of temperature ``temperature`` behind domain face ``face`` (0..5 = ix1 .. ox3); 0 = off.  The
+    face must belong to an active axis and its swarm boundary must not be periodic (checked by the count call,
+    where the mesh is known); a replicated mesh has no boundary source."""
+    if md.replicated and temperature > 0:
+        raise ValueError("the boundary source needs the blocks dealt to the ranks: not with a replicated mesh")
+    _lib.check(md.lib.jb_set_boundary_source(md.pkg.ctx, int(face), float(temperature)))
+    md._bs_temp[int(face)] = float(temperature)
+    _set_boundary_source_count(md)
+
+
+def boundary_source_on(md: MeshData) -> bool:
+    return any(t > 0.0 for t in md._bs_temp)
+
+
+def boundary_face_cells_total(md: MeshData) -> int:
+    """Source face cells of the WHOLE mesh under the faces now set (the same on every rank: from the global mesh)."""
+    m = md.mesh
+    total = 0
+    for f, t in enumerate(md._bs_temp):
+        d = f >> 1
+        if not t > 0.0 or d >= m.ndim:
+            continue
+        half = 0.5 * m.blk_dx[:, d]
+        on = (m.blk_xmax[:, d] > m.gmax[d] - half) if f & 1 else (m.blk_xmin[:, d] < m.gmin[d] + half)
+        total += int(on.sum()) * (m.ncell // int(m.nx[d]))
+    return total
+
+
+def _set_boundary_source_count(md: MeshData) -> None:
+    # (what the library's own step calls -- JB_HANDOFF=step -- ask for)
+    _lib.check(md.lib.jb_set_boundary_source_count(md.pkg.ctx, int(md.bsource_num_particles),
+                                                   boundary_face_cells_total(md)))
+
+
+def _count_boundary(md: MeshData, dt: float):
+    """jb_source_boundary_count: (photons per resident block, the rank's record)."""
+    if md.replicated:
+        raise ValueError("the boundary source needs the blocks dealt to the ranks: not with a replicated mesh")
+    words = int(md.lib.jb_boundary_prefix_words(md.handle))
+    if md._bs_prefix is None or md._bs_prefix.numel() < words:
+        md._bs_prefix = torch.zeros(words, dtype=torch.int32, device=md.device)
+    nper = np.zeros(md.nblocks, dtype=np.int32)
+    plan = _lib.BoundarySourcePlan(nper_block=nper.ctypes.data)
+    md._sync_stream()
+    _lib.check(md.lib.jb_source_boundary_count(md.pkg.ctx, md.handle, dt, boundary_face_cells_total(md),
+                                               int(md.bsource_num_particles), source_epoch(md.cycle, SourceType.emission),
+                                               C.byref(plan), md._bs_prefix.data_ptr()))
+    return nper, dict(e_face=[float(v) for v in plan.e_face], n_face=[int(v) for v in plan.n_face])
+
+
+def _source_emission_and_count_boundary(md: MeshData, nper_em: np.ndarray, t_start: float, dt: float) -> TaskStatus:
+    """The emission source's fill with the boundary source on: block b takes ``n_em[b] + n_bs[b]`` consecutive ids,
+    the emission photons first (include/jaybenne_amd.hpp: PlanSourceWithBoundary).  The boundary photons are counted
+    here and filled by ``SourceBoundaryPhotons``."""
+    pkg = md.pkg
+    nper_bs, rec = _count_boundary(md, dt)
+    counts = _global_block_counts(md, nper_em.astype(np.int64) + nper_bs)
+    excl = np.concatenate(([0], np.cumsum(counts)[:-1]))
+    id_base = np.ascontiguousarray(md.next_id + excl[md.resident_gids], dtype=np.uint64)
+    local_excl = np.concatenate(([0], np.cumsum(nper_em.astype(np.int64))[:-1]))
+    slot_base = np.ascontiguousarray(md.n + local_excl, dtype=np.int64)
+    tot = int(nper_em.sum())
+    md.reserve(md.n + tot + int(nper_bs.sum()))
+    _lib.check(md.lib.jb_source_photons_fill(pkg.ctx, md.handle, C.byref(md.sv), int(SourceType.emission),
+                                             t_start, dt, nper_em.ctypes.data, md.prefix.data_ptr(),
+                                             slot_base.ctypes.data, id_base.ctypes.data))
+    md.sv.n += tot
+    md.next_id += int(counts.sum())
+    md._bs_plan = dict(nper=nper_bs, id_base=np.ascontiguousarray(id_base + nper_em.astype(np.uint64), dtype=np.uint64),
+                       rec=rec, cycle=md.cycle)
+    return TaskStatus.complete
+
+
+def SourceBoundaryPhotons(md: MeshData, t_start: float, dt: float) -> TaskStatus:
+    """The boundary source of one cycle, right behind ``SourcePhotons(emission)``: every source face cell emits
+    ``sb T_f^4 A dt`` in photons born ``eps_imc dx`` inside it with a cosine-law inward direction
+    (include/jaybenne_amd.h).  Appends the cycle's record -- ``e_face`` / ``n_face``, summed over the ranks -- to
+    ``md.boundary_source_history``.  With every face off: nothing, and no kernel."""
+    if not boundary_source_on(md):
+        return TaskStatus.complete
+    pkg = md.pkg
+    plan, md._bs_plan = md._bs_plan, None
+    if plan is None or plan["cycle"] != md.cycle:      # (no emission source in front: the boundary photons alone)
+        nper, rec = _count_boundary(md, dt)
+        counts = _global_block_counts(md, nper)
+        excl = np.concatenate(([0], np.cumsum(counts)[:-1]))
+        plan = dict(nper=nper, id_base=np.ascontiguousarray(md.next_id + excl[md.resident_gids], dtype=np.uint64),
+                    rec=rec)
+        md.next_id += int(counts.sum())
+    nper = plan["nper"]
+    local_excl = np.concatenate(([0], np.cumsum(nper.astype(np.int64))[:-1]))
+    slot_base = np.ascontiguousarray(md.n + local_excl, dtype=np.int64)
+    tot = int(nper.sum())
+    md.reserve(md.n + tot)
+    md._sync_stream()
+    _lib.check(md.lib.jb_source_boundary_fill(pkg.ctx, md.handle, C.byref(md.sv), t_start, dt, nper.ctypes.data,
+                                              md._bs_prefix.data_ptr(), slot_base.ctypes.data,
+                                              plan["id_base"].ctypes.data))
+    md.sv.n += tot
+    _record_boundary_source(md, plan["rec"])
+    return TaskStatus.complete
+
+
+def _record_boundary_source(md: MeshData, rec: dict) -> None:
+    """One cycle's per-face sourced energy and photons, summed over the ranks (in rank order: the same bits on all)."""
+    e, n = np.array(rec["e_face"]), np.array(rec["n_face"], dtype=np.int64)
+    if md.comm is not None and md.nranks > 1:
+        both = np.zeros((md.nranks, 12), dtype=np.int64)
+        both[md.rank, :6] = e.view(np.int64)
+        both[md.rank, 6:] = n
+        both = md.comm.allreduce_sum_int64(both.reshape(-1)).reshape(md.nranks, 12)
+        e = np.zeros(6)
+        for r in range(md.nranks):
+            e = e + both[r, :6].copy().view(np.float64)
+        n = both[:, 6:].sum(axis=0)
+    md.boundary_source_history.append(dict(cycle=md.cycle, e_face=[float(v) for v in e], n_face=[int(v) for v in n]))
 
 
 def _transport(md: MeshData, t_start: float, dt: float, first: int, last: Optional[int],
@@ -853,6 +986,8 @@ def _radiation_step_ranks(md: MeshData, t_start: float, dt: float) -> TaskStatus
     ledger = md.ledger_enabled()
     if ledger:
         md._ledger_begin(t_start)
+    if boundary_source_on(md):
+        _set_boundary_source_count(md)
     md._sync_stream()
     next_id, cycle, rep = C.c_uint64(md.next_id), C.c_uint32(md.cycle), _lib.StepReport()
     st = md.lib.jb_radiation_step_ranks(pkg.ctx, md.handle, C.byref(md.sv), t_start, dt, C.byref(next_id),
@@ -874,6 +1009,10 @@ def _radiation_step_ranks(md: MeshData, t_start: float, dt: float) -> TaskStatus
     if st == _lib.JB_ITERATE:
         return TaskStatus.iterate
     md.events += int(rep.events)
+    if boundary_source_on(md):     # (sourced inside the call, behind the emission source)
+        last = _lib.BoundarySourceRecord()
+        _lib.check(md.lib.jb_boundary_source_last(pkg.ctx, C.byref(last)))
+        _record_boundary_source(md, dict(e_face=list(last.e_face), n_face=list(last.n_face)))
     if ledger:     # (closed and reduced over the ranks inside the call)
         led = _lib.EnergyLedger()
         _lib.check(md.lib.jb_ledger_last(pkg.ctx, C.byref(led)))
@@ -932,6 +1071,7 @@ def _radiation_step(md: MeshData, t_start: float, dt: float) -> TaskStatus:
         UpdateDerivedTransportFields(md, dt)
         n_before = md.n
         SourcePhotons(md, SourceType.emission, t_start, dt)
+        SourceBoundaryPhotons(md, t_start, dt)
         if ledger and md.n > n_before:
             _lib.check(md.lib.jb_ledger_accumulate(pkg.ctx, md.handle, C.byref(md.sv), n_before, md.n,
                                                    _lib.JB_LEDGER_SOURCED))

@@ -320,6 +320,16 @@ class McblockDriver:
         order = deck_cell_order(pin)
         if order != self.md.cell_order:
             self.md.cell_order = order
+        # (nor these: the boundary source -- a black wall of temperature bsource_<face>_temperature behind a domain
+        # face, bsource_num_particles photons per cycle over all such faces; every temperature 0 = off)
+        self.md.bsource_num_particles = pin.GetOrAddInteger("jaybenne_amd", "bsource_num_particles", 0)
+        for f, name in enumerate(jb.FACE_NAMES):
+            temp = pin.GetOrAddReal("jaybenne_amd", f"bsource_{name}_temperature", 0.0)
+            if temp != 0.0:
+                if replicated:
+                    raise ValueError(f"bsource_{name}_temperature: the boundary source needs the blocks dealt to the "
+                                     "ranks; a replicated mesh holds every block on every rank")
+                jb.SetBoundarySource(self.md, f, temp)
         if ledger is None:
             ledger = pin.GetOrAddBoolean("jaybenne_amd", "ledger", False) or self.md.ledger_enabled()
         if bool(ledger) != self.md.ledger_enabled():
