@@ -20,7 +20,10 @@
 // the scattering mean-free-path array holds a negative number whose low word is the byte offset of
 // the cell a photon stepping into it really is in (k_lam_ghost_codes, once per mesh: the first
 // interior cell of the same-level resident neighbour, of the block across a periodic boundary, or,
-// at a reflecting wall, the cell it came from, position and direction mirrored).  The value
+// at a reflecting wall, the cell it came from, position and direction mirrored).  The datum is
+// requested only by a step that put the photon through a cell face (and by every path that sets the
+// offset itself: ghost code, wall, level change, relocation, refill) -- a scatter, an absorption or a
+// census inside the cell leaves the lane holding its cell's values.  The value
 // requested at the end of a pass is looked at in the next one; a lane that finds such a number
 // takes the offset, requests that cell's datum and sits the pass out (0.36 % of the events of
 // BASELINE configs[1]) -- p does not change across a face between blocks of one size, and the block
@@ -418,14 +421,23 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
       })
       if (stepping JB_INV_STMT(&& !inv_bad)) {
         bool is_absorbed, is_scattered, hit_any;
+        unsigned long long hit_m;
         imc_step_cell<NDIM, NOABS, UNIFORM, kWide>(cg, sy, sz, lam_a, lam_s, rng, drem, px, py, pz, ox, oy, oz, qoff,
-                                            is_absorbed, is_scattered, hit_any);
-        fetch_lam();  // (for the next pass, ahead of the scatter)
+                                            is_absorbed, is_scattered, hit_any, &hit_m);
+        // (for the next pass, ahead of the scatter -- and only where the step changed the cell: a lane that
+        // scattered, was absorbed or reached census inside its cell holds that cell's values already; on
+        // BASELINE configs[1] 72 % of the steps.  The scalar OR of the step's three hit masks goes into
+        // exec around the load: no vector instruction, the live registers are the load's destination.  The
+        // wave's at_face lanes are formed from the comparisons' ballots as scalars, ahead of the masked
+        // load: asked for behind it, the ballot of the conjunction goes through a vector register)
         const bool census = !(drem > 0.0);
         bool collide = is_absorbed || is_scattered;
         bool off = false;
         const bool at_face = hit_any && (collide || census);
-        if (__builtin_amdgcn_ballot_w64(at_face) != 0ull) {
+        const unsigned long long at_face_m =
+            hit_m & (__builtin_amdgcn_ballot_w64(collide) | __builtin_amdgcn_ballot_w64(census));
+        if (hit_any) fetch_lam();
+        if (at_face_m != 0ull) {
           // a collision or the census within eps of a cell face (one event in ~1e8): if that face is
           // a block face the reference relocates the photon first (and forgets the collision,
           // transport.cpp:149-155).  (A branch of its own: the test waits for the value just requested.)

@@ -78,6 +78,14 @@ __device__ __forceinline__ double m_min(double a, double b) {
   return d;
 }
 
+// ... with the first operand wave-uniform, read from its SCALAR register pair (a VOP3 v_min_f64 reads one): the
+// "v" form above first copies such an operand into a vector register pair
+__device__ __forceinline__ double m_min_s(double a_uniform, double b) {
+  double d;
+  asm("v_min_f64 %0, %1, %2" : "=v"(d) : "s"(a_uniform), "v"(b));
+  return d;
+}
+
 // cell index inside one block's [nk][nj][ni] array.  jb_mesh_create checks ni < 2^23 and
 // nj nk < 2^23, so both products are 24-bit multiplications (v_mad_i32_i24, full rate; a
 // general 32-bit multiply-add is a quarter-rate 64-bit one on gfx950).

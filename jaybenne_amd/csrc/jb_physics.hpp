@@ -429,7 +429,8 @@ __device__ __forceinline__ double nudged(double p, double m, bool hit) {
 //   move                         p = fma(omega, d, p)
 //   nudge + Xtoijk               |p| > h - eps_imc dx  ->  p = -+(h - eps_imc dx), offset +- stride
 // hit_any: the photon was put through a cell face (the caller then knows that a collision or the
-// census of this step may have happened next to a BLOCK face).
+// census of this step may have happened next to a BLOCK face, and that the cell offset changed);
+// hit_mask, where asked for: hit_any of the wave's lanes.
 struct CellGeom {
   double hx, hy, hz, mx, my, mz, dxp;
 };
@@ -437,7 +438,8 @@ template <int NDIM, bool NOABS, bool UNIFORM = false, bool WIDELOG = false, clas
 __device__ __forceinline__ void imc_step_cell(const CellGeom &g, int sy, int sz, double lam_a, double lam_s,
                                               Rng &rng, double &drem, double &px, double &py, double &pz,
                                               double ox, double oy, double oz, unsigned &qoff,
-                                              bool &is_absorbed, bool &is_scattered, bool &hit_any) {
+                                              bool &is_absorbed, bool &is_scattered, bool &hit_any,
+                                              unsigned long long *hit_mask = nullptr) {
   constexpr bool multi_d = NDIM >= 2, three_d = NDIM == 3;
   constexpr int sx = 8;
   // ---- transport_utils.hpp:118-134: distances to collision, census, cell faces
@@ -445,7 +447,12 @@ __device__ __forceinline__ void imc_step_cell(const CellGeom &g, int sy, int sz,
   if constexpr (NOABS) rng.skip();
   else dx_abs = -lam_a * m_log_lean<true, WIDELOG>(rng.drand());
   const double dx_sc = -lam_s * m_log_lean<true, WIDELOG>(rng.drand());
+#ifdef JB_IMC_NO_SCALAR_MIN
   double dx_push = m_min(g.dxp, drem);
+#else
+  // (wave-uniform geometry: the smallest cell width is read from its scalar register pair)
+  double dx_push = UNIFORM ? m_min_s(g.dxp, drem) : m_min(g.dxp, drem);
+#endif
   double rx, ry = 0.0, rz = 0.0;
   if constexpr (three_d) {
     // the three reciprocals from ONE hardware reciprocal, of the product (imc_step_dir)
@@ -493,6 +500,14 @@ __device__ __forceinline__ void imc_step_cell(const CellGeom &g, int sy, int sz,
     pz = nudged<UNIFORM>(pz, g.mz, hit_z);
   }
   hit_any = hit_x || hit_y || hit_z;
+  // (hit_any of every lane as a wave mask: the three comparisons' ballots ORed as scalars -- the ballot of a
+  // disjunction goes through a vector register)
+  if (hit_mask) {
+    unsigned long long m = __builtin_amdgcn_ballot_w64(hit_x);
+    if (multi_d) m |= __builtin_amdgcn_ballot_w64(hit_y);
+    if (three_d) m |= __builtin_amdgcn_ballot_w64(hit_z);
+    *hit_mask = m;
+  }
 }
 
 // A crossing into a resident block one level coarser or finer, in cell-local coordinates
