@@ -71,6 +71,12 @@ namespace jb {
 #ifndef JB_IMC_NT_STORES
 #define JB_IMC_NT_STORES 0
 #endif
+// The step's nudge and re-indexing under one exec mask per axis (jb_physics.hpp: nudge_reindex_masked), 6 instead
+// of 8 vector instructions per axis: every instantiation (C2 52.96 -> 50.59, C4 42.36 -> 41.00 ms per step; registers
+// and scratch unchanged in all of them).  0 = the select form with its inline-asm v_bfi_b32 / v_cndmask_b32.
+#ifndef JB_IMC_MASKED_NUDGE
+#define JB_IMC_MASKED_NUDGE 1
+#endif
 #ifndef JB_IMC_SERVICE_BUDGET
 #define JB_IMC_SERVICE_BUDGET 96
 #endif
@@ -120,6 +126,8 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
   }
   // (a non-absorbing material only: with the absorption logarithm beside it the 3-D form spills registers)
   constexpr bool kWide = kWideLog && NOABS;
+  // the step's nudge and re-indexing under exec masks (jb_physics.hpp: nudge_reindex_masked)
+  constexpr bool kMasked = JB_IMC_MASKED_NUDGE != 0;
   load_math_tables<false, !kWide, false, true, kWide>();  // lean logarithm, sincos of 2 pi u (ends with a barrier)
 
   constexpr int kServiceBudget = JB_IMC_SERVICE_BUDGET;
@@ -422,21 +430,23 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
       if (stepping JB_INV_STMT(&& !inv_bad)) {
         bool is_absorbed, is_scattered, hit_any;
         unsigned long long hit_m;
-        imc_step_cell<NDIM, NOABS, UNIFORM, kWide>(cg, sy, sz, lam_a, lam_s, rng, drem, px, py, pz, ox, oy, oz, qoff,
-                                            is_absorbed, is_scattered, hit_any, &hit_m);
+        imc_step_cell<NDIM, NOABS, UNIFORM, kWide, kMasked>(cg, sy, sz, lam_a, lam_s, rng, drem, px, py, pz, ox, oy, oz,
+                                                     qoff, is_absorbed, is_scattered, hit_any, &hit_m, fetch_lam);
         // (for the next pass, ahead of the scatter -- and only where the step changed the cell: a lane that
         // scattered, was absorbed or reached census inside its cell holds that cell's values already; on
         // BASELINE configs[1] 72 % of the steps.  The scalar OR of the step's three hit masks goes into
-        // exec around the load: no vector instruction, the live registers are the load's destination.  The
-        // wave's at_face lanes are formed from the comparisons' ballots as scalars, ahead of the masked
-        // load: asked for behind it, the ballot of the conjunction goes through a vector register)
-        const bool census = !(drem > 0.0);
+        // exec around the load -- imc_step_cell issues it, through fetch_lam, once the offset names the new
+        // cell: no vector instruction, the live registers are the load's destination.  The wave's at_face
+        // lanes are formed from the comparisons' ballots as scalars: the ballot of the conjunction goes
+        // through a vector register)
+        const bool alive = drem > 0.0, census = !alive;
         bool collide = is_absorbed || is_scattered;
         bool off = false;
-        const bool at_face = hit_any && (collide || census);
+        // (census as the complement of `alive`'s ballot: hit_m holds stepping lanes only; a lane's at_face is its
+        // bit of the mask)
         const unsigned long long at_face_m =
-            hit_m & (__builtin_amdgcn_ballot_w64(collide) | __builtin_amdgcn_ballot_w64(census));
-        if (hit_any) fetch_lam();
+            hit_m & (__builtin_amdgcn_ballot_w64(collide) | ~__builtin_amdgcn_ballot_w64(alive));
+        const bool at_face = __builtin_amdgcn_inverse_ballot_w64(at_face_m);
         if (at_face_m != 0ull) {
           // a collision or the census within eps of a cell face (one event in ~1e8): if that face is
           // a block face the reference relocates the photon first (and forgets the collision,

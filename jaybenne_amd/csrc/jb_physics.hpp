@@ -421,6 +421,74 @@ __device__ __forceinline__ double nudged(double p, double m, bool hit) {
 #endif
 }
 
+// The nudge and the re-indexing under exec masks instead of selects.  Per axis ONE comparison, |p| > m, whose
+// result the hardware leaves as a wave mask in a scalar register pair; with that mask in exec the crossing lanes
+// alone run
+//   v_med3_i32     side = clamp(high word of p, -1, 1)     (+-1 by the sign of p: the word is never 0 where |p| > m)
+//   v_mad_i32_i24  offset += side * stride                 (the stride a scalar operand)
+//   v_bfi_b32 / v_xor_b32 / v_mov_b32                      p = -copysign(m, p), word by word
+// -- 6 vector instructions per axis instead of the select form's 8 (comparison, three for the side, multiply-add,
+// v_bfi_b32 and two selects), three of them plain 32-bit operations.  The bits are the select form's; a lane
+// whose comparison is false (NaN included) is not written.  One statement for all axes: exec is saved and
+// restored inside it -- the compiler never sees it changed -- and every mask is ANDed with the saved value, so a
+// lane that is not stepping is never written: 4 scalar instructions in 3-D.
+// -DJB_NO_ASM_NUDGE keeps every kernel on the select form, written in plain C++
+// (tests/test_gpu_imc_nudge.py compares the two bit for bit).
+#ifdef JB_NO_ASM_NUDGE
+constexpr bool kMaskedNudge = false;
+#else
+constexpr bool kMaskedNudge = true;
+#endif
+typedef unsigned long long lane_mask;
+#define JB_NUDGE_AXIS(a)                                                                      \
+  "v_med3_i32 %[t], %[h" a "], -1, 1\n\tv_mad_i32_i24 %[q], %[t], %[s" a "], %[q]\n\t"        \
+  "v_bfi_b32 %[h" a "], %[k], %[mh" a "], %[h" a "]\n\tv_xor_b32_e32 %[h" a "], 0x80000000, %[h" a "]\n\t" \
+  "v_mov_b32_e32 %[l" a "], %[ml" a "]\n\t"
+template <int NDIM>
+__device__ __forceinline__ void nudge_reindex_masked(double &px, double &py, double &pz, unsigned &qoff, double mx,
+                                                     double my, double mz, int sy, int sz, lane_mask hx,
+                                                     lane_mask hy, lane_mask hz) {
+  lane_mask sv;
+  int t;
+  int hix = __double2hiint(px), lox = __double2loint(px);
+  if constexpr (NDIM == 1) {
+    asm("s_and_saveexec_b64 %[sv], %[mx]\n\t" JB_NUDGE_AXIS("x") "s_mov_b64 exec, %[sv]"
+        : [sv] "=&s"(sv), [t] "=&v"(t), [q] "+v"(qoff), [hx] "+v"(hix), [lx] "+v"(lox)
+        : [mx] "s"(hx), [k] "s"(0x7fffffff), [sx] "n"(8), [mhx] "v"(__double2hiint(mx)),
+          [mlx] "v"(__double2loint(mx))
+        : "scc");
+  } else if constexpr (NDIM == 2) {
+    int hiy = __double2hiint(py), loy = __double2loint(py);
+    asm("s_and_saveexec_b64 %[sv], %[mx]\n\t" JB_NUDGE_AXIS("x")
+        "s_and_b64 exec, %[sv], %[my]\n\t" JB_NUDGE_AXIS("y") "s_mov_b64 exec, %[sv]"
+        : [sv] "=&s"(sv), [t] "=&v"(t), [q] "+v"(qoff), [hx] "+v"(hix), [lx] "+v"(lox), [hy] "+v"(hiy),
+          [ly] "+v"(loy)
+        : [mx] "s"(hx), [my] "s"(hy), [k] "s"(0x7fffffff), [sx] "n"(8), [sy] "s"(sy),
+          [mhx] "v"(__double2hiint(mx)), [mlx] "v"(__double2loint(mx)), [mhy] "v"(__double2hiint(my)),
+          [mly] "v"(__double2loint(my))
+        : "scc");
+    py = __hiloint2double(hiy, loy);
+  } else {
+    int hiy = __double2hiint(py), loy = __double2loint(py), hiz = __double2hiint(pz), loz = __double2loint(pz);
+    asm("s_and_saveexec_b64 %[sv], %[mx]\n\t" JB_NUDGE_AXIS("x")
+        "s_and_b64 exec, %[sv], %[my]\n\t" JB_NUDGE_AXIS("y")
+        "s_and_b64 exec, %[sv], %[mz]\n\t" JB_NUDGE_AXIS("z") "s_mov_b64 exec, %[sv]"
+        : [sv] "=&s"(sv), [t] "=&v"(t), [q] "+v"(qoff), [hx] "+v"(hix), [lx] "+v"(lox), [hy] "+v"(hiy),
+          [ly] "+v"(loy), [hz] "+v"(hiz), [lz] "+v"(loz)
+        : [mx] "s"(hx), [my] "s"(hy), [mz] "s"(hz), [k] "s"(0x7fffffff), [sx] "n"(8), [sy] "s"(sy), [sz] "s"(sz),
+          [mhx] "v"(__double2hiint(mx)), [mlx] "v"(__double2loint(mx)), [mhy] "v"(__double2hiint(my)),
+          [mly] "v"(__double2loint(my)), [mhz] "v"(__double2hiint(mz)), [mlz] "v"(__double2loint(mz))
+        : "scc");
+    py = __hiloint2double(hiy, loy);
+    pz = __hiloint2double(hiz, loz);
+  }
+  px = __hiloint2double(hix, lox);
+}
+#undef JB_NUDGE_AXIS
+struct NoGather {
+  __device__ __forceinline__ void operator()() const {}
+};
+
 // The lean tracking step of transport_utils.hpp:118-159 + Xtoijk (transport.cpp:146) in CELL-LOCAL
 // coordinates (jb_kernel_imc.hpp states the representation: p = x - cell centre per axis, unit
 // direction omega, distance left to census, byte offset of the cell with byte strides 8 / sy / sz per
@@ -434,12 +502,15 @@ __device__ __forceinline__ double nudged(double p, double m, bool hit) {
 struct CellGeom {
   double hx, hy, hz, mx, my, mz, dxp;
 };
-template <int NDIM, bool NOABS, bool UNIFORM = false, bool WIDELOG = false, class Rng>
+// MASKED: the nudge and the re-indexing under exec masks (nudge_reindex_masked above) instead of selects;
+// `gather`, where given, is called on the lanes of hit_any once the offset names the new cell.
+template <int NDIM, bool NOABS, bool UNIFORM = false, bool WIDELOG = false, bool MASKED = false, class Rng,
+          class Gather = NoGather>
 __device__ __forceinline__ void imc_step_cell(const CellGeom &g, int sy, int sz, double lam_a, double lam_s,
                                               Rng &rng, double &drem, double &px, double &py, double &pz,
                                               double ox, double oy, double oz, unsigned &qoff,
                                               bool &is_absorbed, bool &is_scattered, bool &hit_any,
-                                              unsigned long long *hit_mask = nullptr) {
+                                              unsigned long long *hit_mask = nullptr, Gather gather = Gather()) {
   constexpr bool multi_d = NDIM >= 2, three_d = NDIM == 3;
   constexpr int sx = 8;
   // ---- transport_utils.hpp:118-134: distances to collision, census, cell faces
@@ -482,6 +553,19 @@ __device__ __forceinline__ void imc_step_cell(const CellGeom &g, int sy, int sz,
   px = fma(ox, dx_move, px);
   if (multi_d) py = fma(oy, dx_move, py);
   if (three_d) pz = fma(oz, dx_move, pz);
+  if constexpr (MASKED && kMaskedNudge) {
+    // (the comparisons as wave masks; a lane's hit_any is its bit of their scalar OR, read back as a lane
+    // predicate -- no vector instruction)
+    const lane_mask hx = __builtin_amdgcn_ballot_w64(fabs(px) > g.mx);
+    const lane_mask hy = multi_d ? __builtin_amdgcn_ballot_w64(fabs(py) > g.my) : 0ull;
+    const lane_mask hz = three_d ? __builtin_amdgcn_ballot_w64(fabs(pz) > g.mz) : 0ull;
+    const lane_mask hm = hx | hy | hz;
+    hit_any = __builtin_amdgcn_inverse_ballot_w64(hm);
+    if (hit_mask) *hit_mask = hm;
+    nudge_reindex_masked<NDIM>(px, py, pz, qoff, g.mx, g.my, g.mz, sy, sz, hx, hy, hz);
+    if (hit_any) gather();
+    return;
+  }
   const bool hit_x = fabs(px) > g.mx;
   const bool hit_y = multi_d && fabs(py) > g.my;
   const bool hit_z = three_d && fabs(pz) > g.mz;
@@ -508,6 +592,7 @@ __device__ __forceinline__ void imc_step_cell(const CellGeom &g, int sy, int sz,
     if (three_d) m |= __builtin_amdgcn_ballot_w64(hit_z);
     *hit_mask = m;
   }
+  if (hit_any) gather();
 }
 
 // A crossing into a resident block one level coarser or finer, in cell-local coordinates
