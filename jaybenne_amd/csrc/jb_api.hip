@@ -1342,6 +1342,12 @@ static void launch_k_imc_cell(jb_context *ctx, const jb_mesh *mesh, const Transp
   });
 }
 
+// the heads of the launch's particle queues (jb_scaffold.hpp: QueueCursor) back to zero, in stream order in front of
+// every persistent tracking launch
+static void clear_queue_heads(jb_context *ctx) {
+  (void)hipMemsetAsync(ctx->counters_d + CNT_QUEUE, 0, kQueues * kQueueStride * sizeof(unsigned long long), ctx->stream);
+}
+
 // k_hybrid<NDIM, TALLY, NOABS, MODE, PHASE> on entries [f, l) of list_in (nullptr: slots of the swarm), with the
 // queue heads cleared in front of it; PHASE 2 exists as <.., true, 0, 2> only (hybrid_phase)
 template <int NDIM>
@@ -1349,7 +1355,7 @@ static void launch_k_hybrid(jb_context *ctx, const jb_mesh *mesh, const Transpor
                             const DevSwarm &S, double t_start, double dt, long long f, long long l,
                             const unsigned *list_in, unsigned *list_out, unsigned long long *count_out,
                             const unsigned long long *count_in) {
-  (void)hipMemsetAsync(ctx->counters_d + CNT_QUEUE, 0, kQueues * kQueueStride * sizeof(unsigned long long), ctx->stream);
+  clear_queue_heads(ctx);
   const HybridPhase h = hybrid_phase(p, phase);
   with_bool(p.tally, [&](auto tc) {
     with_bool(h.noabs, [&](auto nc) {
@@ -1436,7 +1442,7 @@ static jb_status launch_transport(jb_context *ctx, jb_mesh *mesh, const DevSwarm
                                   long long first, long long last, bool tally, bool ddmc) {
   const DevMesh &M = mesh->dm;
   const bool gray = M.lam_abs != nullptr;
-  (void)hipMemsetAsync(ctx->counters_d + CNT_QUEUE, 0, kQueues * kQueueStride * sizeof(unsigned long long), ctx->stream);
+  clear_queue_heads(ctx);
   // (the one input the device holds: whether every cell takes DDMC steps, and the number of distinct step
   // records, as UpdateDerivedTransportFields left them)
   if (ddmc && gray && M.ddmc_cell && M.nblocks <= kLdsBlocks && mesh->not_all_ddmc_host < 0) {

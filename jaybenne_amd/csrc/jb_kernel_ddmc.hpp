@@ -173,11 +173,11 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD) JB_DDMC_AL
   // (16-byte aligned: the record table carved out of it is read as 32-byte vectors, ds_read_b128)
   extern __shared__ __attribute__((aligned(16))) double lds_dyn[];
   double *const lds_tally = lds_dyn;
-  const bool tally_in_lds = TALLY && (long long)M.nblocks * M.ntot <= (long long)kLdsTally;
+  const bool tally_in_lds = lds_tally_fits<TALLY>(M);
   const int ncell_all = M.nblocks * (int)M.ntot;
   // (behind the tally, on a 16-byte boundary)
   const double *const lds_rec_tab = lds_dyn + (tally_in_lds ? (ncell_all + 1) / 2 * 2 : 0);
-  if constexpr (TALLY) {
+  if constexpr (TALLY) {  // (lds_tally_zero, with the count at hand)
     if (tally_in_lds)
       for (int q = threadIdx.x; q < ncell_all; q += blockDim.x) lds_tally[q] = 0.0;
   }
@@ -203,11 +203,8 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD) JB_DDMC_AL
   const double vv = P.c;
   const double t_end = t_start + dt;
   const int lane = threadIdx.x & 63;
-  unsigned long long *queue = counters + CNT_QUEUE;
-  const long long per_q = (last - first + kQueues - 1) / kQueues;
-  int cur = blockIdx.x % kQueues, tried = 0;
-  bool more = true;
-  long long chunk_pos = 0, chunk_end = 0;
+  QueueCursor qcur(counters, first, last);
+  long long chunk_pos = 0, chunk_end = 0;   // the wave's chunk (refill_chunk)
 
   // wave-level counters (scalar registers; updated outside divergent branches): finished histories
   // by outcome; events = running lanes summed over the event-loop passes + service-phase steps
@@ -423,22 +420,8 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD) JB_DDMC_AL
       pf_src = (win_head + rank) & 63;
     } else {
       unsigned long long need = __ballot(ls == DS_IDLE || ls == DS_DONE);
-      while (need != 0ull && more) {
-        if (chunk_pos >= chunk_end) {
-          const long long q_first = first + (long long)cur * per_q;
-          long long q_last = q_first + per_q;
-          if (q_last > last) q_last = last;
-          unsigned long long base = 0;
-          if (lane == 0) base = atomicAdd(&queue[cur * kQueueStride], (unsigned long long)kChunk);
-          chunk_pos = q_first + (long long)uniform_u64(base);
-          chunk_end = chunk_pos + kChunk < q_last ? chunk_pos + kChunk : q_last;
-          if (chunk_pos >= q_last) {  // this queue is drained: move on
-            chunk_pos = chunk_end = 0;
-            cur = (cur + 1) % kQueues;
-            if (++tried == kQueues) more = false;
-            continue;
-          }
-        }
+      while (need != 0ull && qcur.more) {
+        if (!refill_chunk<kChunk>(qcur, chunk_pos, chunk_end, lane)) continue;
         const int want = __popcll(need);
         const long long avail = chunk_end - chunk_pos;
         const int give = (long long)want < avail ? want : (int)avail;
@@ -553,20 +536,8 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD) JB_DDMC_AL
       int got = 0;
 #pragma unroll
       for (int sg = 0; sg < 2; ++sg) {
-        while (got < free_n && more && chunk_pos >= chunk_end) {
-          const long long q_first = first + (long long)cur * per_q;
-          long long q_last = q_first + per_q;
-          if (q_last > last) q_last = last;
-          unsigned long long base = 0;
-          if (lane == 0) base = atomicAdd(&queue[cur * kQueueStride], (unsigned long long)kChunk);
-          chunk_pos = q_first + (long long)uniform_u64(base);
-          chunk_end = chunk_pos + kChunk < q_last ? chunk_pos + kChunk : q_last;
-          if (chunk_pos >= q_last) {  // this queue is drained: move on
-            chunk_pos = chunk_end = 0;
-            cur = (cur + 1) % kQueues;
-            if (++tried == kQueues) more = false;
-          }
-        }
+        // (a drained queue: round again on the next one)
+        while (got < free_n && qcur.more && !refill_chunk<kChunk>(qcur, chunk_pos, chunk_end, lane)) {}
         if (got < free_n && chunk_pos < chunk_end) {
           const long long avail = chunk_end - chunk_pos;
           const int give = (long long)(free_n - got) < avail ? free_n - got : (int)avail;
@@ -634,7 +605,7 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD) JB_DDMC_AL
     if (__ballot(ls == DS_DONE || ls == DS_RELOC) != 0ull) continue;
     const int running = __popcll(__ballot(ls == DS_VIRT));
     if (running == 0) {
-      if (more || win_count > 0) continue;   // (PF: the window still holds requested slots)
+      if (qcur.more || win_count > 0) continue;   // (PF: the window still holds requested slots)
       break;
     }
     int waste = 0;
@@ -900,15 +871,7 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD) JB_DDMC_AL
     }
   }
 
-  if constexpr (TALLY) {
-    if (tally_in_lds) {
-      __syncthreads();
-      for (int q = threadIdx.x; q < M.nblocks * (int)M.ntot; q += blockDim.x) {
-        const double v = lds_tally[q];
-        if (v != 0.0) atomicAdd(&M.tally[q / (int)M.ntot][q % (int)M.ntot], v);
-      }
-    }
-  }
+  lds_tally_flush<TALLY>(M, lds_tally, tally_in_lds);
   const unsigned long long r_census = c_census, r_abs = c_abs, r_esc = c_esc, r_out = c_out, r_ev = c_ev - c_ghost;
   if (lane == 0) {
     if (r_census) atomicAdd(&counters[CNT_CENSUS], r_census);

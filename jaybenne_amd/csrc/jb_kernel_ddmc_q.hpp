@@ -81,10 +81,10 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)
   // dynamic shared memory: the tally of a small mesh, then the distinct step records of this cycle
   extern __shared__ __attribute__((aligned(16))) double lds_dyn[];
   double *const lds_tally = lds_dyn;
-  const bool tally_in_lds = TALLY && (long long)M.nblocks * M.ntot <= (long long)kLdsTally;
+  const bool tally_in_lds = lds_tally_fits<TALLY>(M);
   const int ncell_all = M.nblocks * (int)M.ntot;
   double *const lds_cls = lds_dyn + (tally_in_lds ? (ncell_all + 1) / 2 * 2 : 0);
-  if constexpr (TALLY) {
+  if constexpr (TALLY) {  // (lds_tally_zero, with the count at hand)
     if (tally_in_lds)
       for (int q = threadIdx.x; q < ncell_all; q += blockDim.x) lds_tally[q] = 0.0;
   }
@@ -113,17 +113,14 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)
   const double vv = P.c;
   const double t_end = t_start + dt;
   const int lane = threadIdx.x & 63;
-  unsigned long long *queue = counters + CNT_QUEUE;
-  const long long per_q = (last - first + kQueues - 1) / kQueues;
-  int cur = blockIdx.x % kQueues, tried = 0;
-  bool more = true;
-  long long chunk_pos = 0, chunk_end = 0;
+  QueueCursor qcur(counters, first, last);
+  long long chunk_pos = 0, chunk_end = 0;   // the wave's chunk (refill_chunk)
   int ready_cnt = 0, done_cnt = 0;   // (wave-uniform)
 #ifdef JB_DDMC_EXP_SEQSTORE
   long long exp_wr_cur = 0, exp_wr_end = 0;
 #endif
 
-  unsigned int c_census = 0, c_abs = 0, c_esc = 0, c_out = 0;
+  OutcomeCounts done_c;  // (per wave)
   unsigned long long c_ev = 0;
   unsigned int c_pass = 0, c_service = 0;
 
@@ -255,7 +252,7 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)
     // two batches, each at full width: the DONE queue (phase 0), then new photons for the READY queue (phase 1)
     for (int phase = 0; phase < 2; ++phase) {
       JB_QT(phase == 0 ? 2 : 0)
-      if (phase == 0 ? done_cnt == 0 : !(ready_cnt < 64 && more)) continue;
+      if (phase == 0 ? done_cnt == 0 : !(ready_cnt < 64 && qcur.more)) continue;
       ++c_service;
       // ---- one item per lane: what k_ddmc_all's service phase calls the lane's own state
       int ls = DS_IDLE;
@@ -338,13 +335,13 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)
         unsigned long long rng_in = 0ull;
         double t_in = 0.0, x_in = 0.0, y_in = 0.0, z_in = 0.0, vx_in = 0.0, vy_in = 0.0, vz_in = 0.0;
         unsigned long long need = ~0ull;
-        while (need != 0ull && more) {
+        while (need != 0ull && qcur.more) {
+          // (refill_chunk written out: through the helper the 2-D forms of this kernel take 123 instead of 119 registers)
           if (chunk_pos >= chunk_end) {
-            const long long q_first = first + (long long)cur * per_q;
-            long long q_last = q_first + per_q;
-            if (q_last > last) q_last = last;
+            long long q_first, q_last;
+            qcur.range(q_first, q_last);
             unsigned long long base = 0;
-            if (lane == 0) base = atomicAdd(&queue[cur * kQueueStride], (unsigned long long)kChunk);
+            if (lane == 0) base = atomicAdd(qcur.head(), (unsigned long long)kChunk);
             chunk_pos = q_first + (long long)uniform_u64(base);
             chunk_end = chunk_pos + kChunk < q_last ? chunk_pos + kChunk : q_last;
 #ifdef JB_DDMC_EXP_SEQSTORE   // (timing experiment: results are wrong)
@@ -352,8 +349,7 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)
 #endif
             if (chunk_pos >= q_last) {  // this queue is drained: move on
               chunk_pos = chunk_end = 0;
-              cur = (cur + 1) % kQueues;
-              if (++tried == kQueues) more = false;
+              qcur.next();
               continue;
             }
           }
@@ -527,14 +523,7 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)
 #ifdef JB_DDMC_EXP_SEQSTORE
       if (phase == 0) exp_wr_cur += 64;
 #endif
-      {
-        const int n_done = __popcll(__ballot(was_done));
-        const int n_census = __popcll(__ballot(was_done && status == ST_ACTIVE));
-        const int n_abs = __popcll(__ballot(was_done && status == ST_ABSORBED));
-        const int n_esc = __popcll(__ballot(was_done && status == ST_ESCAPED));
-        c_census += n_census; c_abs += n_abs; c_esc += n_esc;
-        c_out += n_done - n_census - n_abs - n_esc;
-      }
+      done_c.count(was_done, status);
       // ---- a particle that sits at a face of its cell (just loaded, or just relocated): handed over to k_hybrid
       //      as it stands
       if (ls == DS_PARK) {
@@ -576,7 +565,7 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)
     retire_refill();
     if (__ballot(r_ls == DS_VIRT) == 0ull) {
       // (nothing to follow: finished histories that found no room, photons still to be loaded, or the end)
-      if (__ballot(r_ls >= DS_DONE) != 0ull || done_cnt > 0 || ready_cnt > 0 || more) continue;
+      if (__ballot(r_ls >= DS_DONE) != 0ull || done_cnt > 0 || ready_cnt > 0 || qcur.more) continue;
       break;
     }
     int waste = 0;
@@ -696,22 +685,14 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)
       if (vm == ~0ull) continue;
       if (vm == 0ull) break;
       if (ready_cnt == 0) {
-        if (more) break;
+        if (qcur.more) break;
         waste += 64 - __popcll(vm);
         if (waste >= JB_DDMC_Q_BUDGET && done_cnt > 0) break;
       }
     }
   }
 
-  if constexpr (TALLY) {
-    if (tally_in_lds) {
-      __syncthreads();
-      for (int q = threadIdx.x; q < M.nblocks * (int)M.ntot; q += blockDim.x) {
-        const double v = lds_tally[q];
-        if (v != 0.0) atomicAdd(&M.tally[q / (int)M.ntot][q % (int)M.ntot], v);
-      }
-    }
-  }
+  lds_tally_flush<TALLY>(M, lds_tally, tally_in_lds);
   // the launch's counters: summed over the workgroup in LDS first (every wave of the launch ends at about the same
   // time, and atomics on ONE line of device memory are served one after the other: 7 per wave were 28,000)
   __shared__ unsigned long long lds_cnt[8];
@@ -719,10 +700,10 @@ __global__ void __launch_bounds__(kBlock, JB_DDMC_ALL_WAVES_PER_SIMD)
   if (threadIdx.x < 8) lds_cnt[threadIdx.x] = 0ull;
   __syncthreads();
   if (lane == 0) {
-    if (c_census) atomicAdd(&lds_cnt[CNT_CENSUS], (unsigned long long)c_census);
-    if (c_abs) atomicAdd(&lds_cnt[CNT_ABSORBED], (unsigned long long)c_abs);
-    if (c_esc) atomicAdd(&lds_cnt[CNT_ESCAPED], (unsigned long long)c_esc);
-    if (c_out) atomicAdd(&lds_cnt[CNT_OUTGOING], (unsigned long long)c_out);
+    if (done_c.census) atomicAdd(&lds_cnt[CNT_CENSUS], (unsigned long long)done_c.census);
+    if (done_c.absorbed) atomicAdd(&lds_cnt[CNT_ABSORBED], (unsigned long long)done_c.absorbed);
+    if (done_c.escaped) atomicAdd(&lds_cnt[CNT_ESCAPED], (unsigned long long)done_c.escaped);
+    if (done_c.outgoing) atomicAdd(&lds_cnt[CNT_OUTGOING], (unsigned long long)done_c.outgoing);
     if (c_ev) atomicAdd(&lds_cnt[CNT_EVENTS], c_ev);
     atomicAdd(&lds_cnt[CNT_PASSES], (unsigned long long)c_pass);
     atomicAdd(&lds_cnt[CNT_SERVICE], (unsigned long long)c_service);

@@ -139,11 +139,8 @@ __global__ void __launch_bounds__(kBlock, PHASE == 0 ? JB_HYBRID_REMAINDER_WAVES
     if (last <= first) return;
   }
   __shared__ double lds_tally[TALLY ? kLdsTally : 1];
-  const bool tally_in_lds = TALLY && (long long)M.nblocks * M.ntot <= (long long)kLdsTally;
-  if constexpr (TALLY) {
-    if (tally_in_lds)
-      for (int q = threadIdx.x; q < M.nblocks * (int)M.ntot; q += blockDim.x) lds_tally[q] = 0.0;
-  }
+  const bool tally_in_lds = lds_tally_fits<TALLY>(M);
+  lds_tally_zero<TALLY>(M, lds_tally, tally_in_lds);
   __shared__ LdsBlockTable lds_blocks;
   fill_block_table(M, lds_blocks);
   load_math_tables();  // (ends with a barrier)
@@ -914,15 +911,7 @@ __global__ void __launch_bounds__(kBlock, PHASE == 0 ? JB_HYBRID_REMAINDER_WAVES
     }
   }
 
-  if constexpr (TALLY) {
-    if (tally_in_lds) {
-      __syncthreads();
-      for (int q = threadIdx.x; q < M.nblocks * (int)M.ntot; q += blockDim.x) {
-        const double v = lds_tally[q];
-        if (v != 0.0) atomicAdd(&M.tally[q / (int)M.ntot][q % (int)M.ntot], v);
-      }
-    }
-  }
+  lds_tally_flush<TALLY>(M, lds_tally, tally_in_lds);
   const unsigned long long r_census = c_census, r_abs = c_abs, r_esc = c_esc, r_out = c_out, r_ev = c_ev;
   if (lane == 0) {
     if (r_census) atomicAdd(&counters[CNT_CENSUS], r_census);

@@ -119,11 +119,8 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
   (void)A.nbr_dq;   // (the face table's byte-offset changes live in the ghost codes of lam_sc since round 4)
   constexpr bool multi_d = NDIM >= 2, three_d = NDIM == 3;
   __shared__ double lds_tally[TALLY ? kLdsTally : 1];
-  const bool tally_in_lds = TALLY && (long long)M.nblocks * M.ntot <= (long long)kLdsTally;
-  if constexpr (TALLY) {
-    if (tally_in_lds)
-      for (int q = threadIdx.x; q < M.nblocks * (int)M.ntot; q += blockDim.x) lds_tally[q] = 0.0;
-  }
+  const bool tally_in_lds = lds_tally_fits<TALLY>(M);
+  lds_tally_zero<TALLY>(M, lds_tally, tally_in_lds);
   // (a non-absorbing material only: with the absorption logarithm beside it the 3-D form spills registers)
   constexpr bool kWide = kWideLog && NOABS;
   // the step's nudge and re-indexing under exec masks (jb_physics.hpp: nudge_reindex_masked)
@@ -134,13 +131,9 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
   const double vv = P.c;
   const double t_end = t_start + dt;
   const int lane = threadIdx.x & 63;
-  unsigned long long *queue = counters + CNT_QUEUE;
-  const long long per_q = (last - first + kQueues - 1) / kQueues;
-  int cur = blockIdx.x % kQueues;
-  int tried = 0;
-  bool more = true;
+  QueueCursor qcur(counters, first, last);
 
-  unsigned int c_census = 0, c_abs = 0, c_esc = 0, c_out = 0;
+  OutcomeCounts done_c;  // (per lane)
   // wave-level (scalar): events in the low 40 bits, passes above them (one 64-bit add per pass)
   unsigned long long c_evp = 0;
   unsigned int c_service = 0;
@@ -298,42 +291,25 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
       JB_WST(&g1(S.status)[n], status);
       JB_WST(&g1(S.rng)[n], (uint64_t)rng.s);
 #undef JB_WST
-      if (status == ST_ACTIVE) {
-        ++c_census;
-        if constexpr (TALLY) {  // jaybenne.cpp:547-561
+      done_c.count(status);
+      if constexpr (TALLY) {  // jaybenne.cpp:547-561
+        if (status == ST_ACTIVE) {
           const double dv = (8.0 * cg.hx) * cg.hy * cg.hz;  // dx dy dz: powers of two, exact in any order
           const int q = (int)((qoff - (unsigned)b * blk_bytes) >> 3);
           if (tally_in_lds) atomicAdd(&lds_tally[b * (int)M.ntot + q], g1(S.w)[n] / dv);
           else atomicAdd(&M.tally[b][q], g1(S.w)[n] / dv);
         }
-      } else if (status == ST_ABSORBED) {
-        ++c_abs;
-      } else if (status == ST_ESCAPED) {
-        ++c_esc;
-      } else {
-        ++c_out;
       }
       ls = IS_IDLE;
       abs_pos = false;
     }
     {
-      // hand new particles to idle lanes: one claim of exactly what they need per service phase
+      // hand new particles to idle lanes: one claim of exactly what they need per service phase (claim_exact)
       const unsigned long long idle = __ballot(ls == IS_IDLE);
-      if (idle != 0ull && more) {
-        const int leader = __ffsll((long long)idle) - 1;
-        const int want = __popcll(idle);
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(&queue[cur * kQueueStride], (unsigned long long)want);
-        base = __shfl(base, leader, 64);
-        const long long q_first = first + (long long)cur * per_q;
-        long long q_last = q_first + per_q;
-        if (q_last > last) q_last = last;
-        const long long cand = q_first + (long long)base + __popcll(idle & ((1ull << lane) - 1ull));
-        if (q_first + (long long)base + want >= q_last) {  // this queue is drained: move on
-          cur = (cur + 1) % kQueues;
-          if (++tried == kQueues) more = false;
-        }
-        if (ls == IS_IDLE && cand < q_last && g1(S.status)[cand] == ST_ACTIVE) {
+      if (idle != 0ull && qcur.more) {
+        long long cand;
+        const bool inside = claim_exact(qcur, idle, lane, cand);
+        if (ls == IS_IDLE && inside && g1(S.status)[cand] == ST_ACTIVE) {
           n = cand;
           rng.s = g1(S.rng)[n];
           b = g1(S.blk)[n];
@@ -361,7 +337,7 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
     }
     const int running = __popcll(__ballot(ls == IS_RUN));
     if (running == 0) {
-      if (__ballot(ls != IS_IDLE) != 0ull || more) continue;
+      if (__ballot(ls != IS_IDLE) != 0ull || qcur.more) continue;
       break;
     }
     int waste = 0;
@@ -476,22 +452,9 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
     }
   }
 
-  if constexpr (TALLY) {
-    if (tally_in_lds) {
-      __syncthreads();
-      for (int q = threadIdx.x; q < M.nblocks * (int)M.ntot; q += blockDim.x) {
-        const double v = lds_tally[q];
-        if (v != 0.0) atomicAdd(&M.tally[q / (int)M.ntot][q % (int)M.ntot], v);
-      }
-    }
-  }
-  unsigned long long r_census = wave_sum(c_census), r_abs = wave_sum(c_abs), r_esc = wave_sum(c_esc),
-                     r_out = wave_sum(c_out);
+  lds_tally_flush<TALLY>(M, lds_tally, tally_in_lds);
+  done_c.flush<true>(counters, lane);
   if (lane == 0) {
-    if (r_census) atomicAdd(&counters[CNT_CENSUS], r_census);
-    if (r_abs) atomicAdd(&counters[CNT_ABSORBED], r_abs);
-    if (r_esc) atomicAdd(&counters[CNT_ESCAPED], r_esc);
-    if (r_out) atomicAdd(&counters[CNT_OUTGOING], r_out);
     atomicAdd(&counters[CNT_EVENTS], c_evp & ((1ull << 40) - 1ull));
     atomicAdd(&counters[CNT_PASSES], c_evp >> 40);
     atomicAdd(&counters[CNT_SERVICE], (unsigned long long)c_service);

@@ -22,32 +22,11 @@
 
 #include "jb_device.hpp"
 #include "jb_invariants.hpp"   // the checked build's JB_INV_* call sites (nothing without JB_INVARIANTS)
+#include "jb_scaffold.hpp"     // queue constants and cursor, LDS tally, outcome counts: shared by the tracking kernels
 
 namespace jb {
 
 constexpr int kBlock = 256;  // 4 waves per workgroup
-
-// counters[]: 0 census, 1 absorbed, 2 escaped, 3 outgoing, 4 events, 5 unfinished
-enum { CNT_CENSUS = 0, CNT_ABSORBED, CNT_ESCAPED, CNT_OUTGOING, CNT_EVENTS, CNT_UNFINISHED, CNT_PASSES, CNT_SERVICE, CNT_N };
-// Heads of the 8 particle queues of the running transport launch, each in a 128-byte line of its own: the claims
-// are returning atomics from every XCD, and atomics on one line are served one after the other -- with the eight
-// heads in ONE line (rounds 1 - 5) and 128-slot claims, BASELINE configs[2] as shipped (12-step histories: 7.8e5
-// claims per 1e8 photons) ran 10.03 ms whatever else was changed; see DESIGN.md 4.2.
-constexpr int CNT_QUEUE = 1024;
-constexpr int kQueueStride = 16;
-constexpr int kQueues = 8;    // one per XCD (workgroups b and b + 8 share an XCD and its L2)
-
-// lane 0's value in every lane, as a wave-uniform (scalar register) quantity
-__device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {
-  const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)v);
-  const unsigned int hi = __builtin_amdgcn_readfirstlane((unsigned int)(v >> 32));
-  return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // interior cell (b, k, j, i) of flat index c over nblocks * ncell
 __device__ __forceinline__ void decode_cell(const DevMesh &M, long long c, int &b, int &k, int &j,
@@ -586,12 +565,8 @@ __global__ void __launch_bounds__(kBlock) k_source_edelta(DevMesh M, int source_
 // runs until enough lanes have left it (see kServiceBudget); keeping the rare, long code paths
 // out of it keeps its 64 lanes on one instruction stream.
 //
-// Particles are dealt from 8 queues, each over one contiguous eighth of the (cell-ordered) swarm
-// (ballot + popcount prefix over the idle mask, one returning atomic per wave).  A workgroup
-// starts on queue blockIdx % 8 -- the workgroups that share an XCD, hence an L2 -- and moves on
-// when its queue is drained, so the particles in flight on one XCD form one short contiguous
-// window of the swarm and the cell data they gather stays in that XCD's 4 MiB L2.  Placement only
-// affects speed, never results.
+// Particles are dealt from 8 queues, each over one contiguous eighth of the (cell-ordered) swarm:
+// jb_scaffold.hpp (QueueCursor, claim_exact, refill_chunk).
 #ifndef JB_TRANSPORT_WAVES_PER_SIMD
 #define JB_TRANSPORT_WAVES_PER_SIMD 1
 #endif
@@ -650,15 +625,9 @@ __launch_bounds__(kBlock, DDMC ? JB_DDMC_WAVES_PER_SIMD
   // (gray DDMC launches come in pairs: k_ddmc_all runs when every cell is a DDMC cell, this
   // kernel when *skip_unless says otherwise)
   if (skip_unless != nullptr && *skip_unless == 0) return;
-  // Small meshes (the reference's 1-D decks: ~1e2 cells under 1e5..1e8 particles): the census
-  // tally of every workgroup goes to LDS and is flushed once at the end, instead of 1e8 global
-  // atomics contending for a handful of cache lines.
-  __shared__ double lds_tally[TALLY ? kLdsTally : 1];
-  const bool tally_in_lds = TALLY && (long long)M.nblocks * M.ntot <= (long long)kLdsTally;
-  if constexpr (TALLY) {
-    if (tally_in_lds)
-      for (int q = threadIdx.x; q < M.nblocks * (int)M.ntot; q += blockDim.x) lds_tally[q] = 0.0;
-  }
+  __shared__ double lds_tally[TALLY ? kLdsTally : 1];  // (small meshes: lds_tally_zero)
+  const bool tally_in_lds = lds_tally_fits<TALLY>(M);
+  lds_tally_zero<TALLY>(M, lds_tally, tally_in_lds);
   // DDMC kernels re-read the block geometry at the top of every event pass (below): from LDS
   __shared__ std::conditional_t<DDMC, LdsBlockTable, int> blk_tab;
   if constexpr (DDMC) fill_block_table(M, blk_tab);
@@ -696,21 +665,15 @@ __launch_bounds__(kBlock, DDMC ? JB_DDMC_WAVES_PER_SIMD
   const double vv = P.c;
   const double t_end = t_start + dt;  // the reference re-evaluates t_start + dt: same double
   const int lane = threadIdx.x & 63;
-  unsigned long long *queue = counters + CNT_QUEUE;  // zeroed by the host before the launch
-  const long long per_q = (last - first + kQueues - 1) / kQueues;
-  int cur = blockIdx.x % kQueues;  // wave-uniform: queue this wave draws from
-  int tried = 0;                   // queues found drained so far
-  bool more = true;                // wave-uniform: some queue may still hold particles
-  // DDMC: slots [chunk_pos, chunk_end) of the swarm are this wave's to deal out (wave-uniform);
-  // short DDMC histories claim 128 at a time (one contended atomic per ~5 service phases); larger
-  // chunks lengthen the tail of a hybrid launch whose IMC histories are ~1e3 events long
+  QueueCursor qcur(counters, first, last);
+  // DDMC: slots [chunk_pos, chunk_end) of the swarm are this wave's to deal out (refill_chunk)
 #ifndef JB_DDMC_CHUNK
 #define JB_DDMC_CHUNK 128
 #endif
   constexpr long long kChunk = JB_DDMC_CHUNK;
   long long chunk_pos = 0, chunk_end = 0;
 
-  unsigned int c_census = 0, c_abs = 0, c_esc = 0, c_out = 0;
+  OutcomeCounts done_c;  // (per lane)
   // wave-level (scalar): events = running lanes summed over the passes, passes, service phases
   unsigned long long c_ev = 0;
   unsigned int c_pass = 0, c_service = 0;
@@ -929,42 +892,23 @@ __launch_bounds__(kBlock, DDMC ? JB_DDMC_WAVES_PER_SIMD
       g1(S.ip)[n] = ip; g1(S.jp)[n] = jp; g1(S.kp)[n] = kp;
       g1(S.status)[n] = status;
       g1(S.rng)[n] = rng.s;
-      if (status == ST_ACTIVE) {
-        ++c_census;
-        if constexpr (TALLY) {  // jaybenne.cpp:547-561
+      done_c.count(status);
+      if constexpr (TALLY) {  // jaybenne.cpp:547-561
+        if (status == ST_ACTIVE) {
           const double dv = B.dx[0] * B.dx[1] * B.dx[2];
           if (tally_in_lds) atomicAdd(&lds_tally[b * (int)M.ntot + cidx(M, kp, jp, ip)], g1(S.w)[n] / dv);
           else atomicAdd(&M.tally[b][cidx(M, kp, jp, ip)], g1(S.w)[n] / dv);
         }
-      } else if (status == ST_ABSORBED) {
-        ++c_abs;
-      } else if (status == ST_ESCAPED) {
-        ++c_esc;
-      } else {
-        ++c_out;
       }
       ls = LS_IDLE;
     }
     if constexpr (!DDMC) {
-      // hand new particles to idle lanes: one claim of exactly what they need per service phase.
-      // IMC histories are ~1e3 events long: this keeps the particles in flight on an XCD one tight
-      // window of the swarm and the tail of the launch short.
+      // hand new particles to idle lanes: one claim of exactly what they need per service phase (claim_exact)
       const unsigned long long idle = __ballot(ls == LS_IDLE);
-      if (idle != 0ull && more) {
-        const int leader = __ffsll((long long)idle) - 1;
-        const int want = __popcll(idle);
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(&queue[cur * kQueueStride], (unsigned long long)want);
-        base = __shfl(base, leader, 64);
-        const long long q_first = first + (long long)cur * per_q;
-        long long q_last = q_first + per_q;
-        if (q_last > last) q_last = last;
-        const long long cand = q_first + (long long)base + __popcll(idle & ((1ull << lane) - 1ull));
-        if (q_first + (long long)base + want >= q_last) {  // this queue is drained: move on
-          cur = (cur + 1) % kQueues;
-          if (++tried == kQueues) more = false;
-        }
-        if (ls == LS_IDLE && cand < q_last && g1(S.status)[cand] == ST_ACTIVE) {
+      if (idle != 0ull && qcur.more) {
+        long long cand;
+        const bool inside = claim_exact(qcur, idle, lane, cand);
+        if (ls == LS_IDLE && inside && g1(S.status)[cand] == ST_ACTIVE) {
           n = cand;
           rng.s = g1(S.rng)[n];
           b = g1(S.blk)[n];
@@ -996,22 +940,8 @@ __launch_bounds__(kBlock, DDMC ? JB_DDMC_WAVES_PER_SIMD
       // prefix over the idle lanes); slots that hold no live particle leave their lane idle for
       // the next round of the loop
       unsigned long long idle = __ballot(ls == LS_IDLE);
-      while (idle != 0ull && more) {
-        if (chunk_pos >= chunk_end) {
-          const long long q_first = first + (long long)cur * per_q;
-          long long q_last = q_first + per_q;
-          if (q_last > last) q_last = last;
-          unsigned long long base = 0;
-          if (lane == 0) base = atomicAdd(&queue[cur * kQueueStride], (unsigned long long)kChunk);
-          chunk_pos = q_first + (long long)uniform_u64(base);
-          chunk_end = chunk_pos + kChunk < q_last ? chunk_pos + kChunk : q_last;
-          if (chunk_pos >= q_last) {  // this queue is drained: move on
-            chunk_pos = chunk_end = 0;
-            cur = (cur + 1) % kQueues;
-            if (++tried == kQueues) more = false;
-            continue;
-          }
-        }
+      while (idle != 0ull && qcur.more) {
+        if (!refill_chunk<kChunk>(qcur, chunk_pos, chunk_end, lane)) continue;
         const int want = __popcll(idle);
         const long long avail = chunk_end - chunk_pos;
         const int give = (long long)want < avail ? want : (int)avail;
@@ -1046,7 +976,7 @@ __launch_bounds__(kBlock, DDMC ? JB_DDMC_WAVES_PER_SIMD
     }
     const int running = __popcll(__ballot(ls == LS_RUN));
     if (running == 0) {
-      if (__ballot(ls != LS_IDLE) != 0ull || more) continue;  // pending service / more to load
+      if (__ballot(ls != LS_IDLE) != 0ull || qcur.more) continue;  // pending service / more to load
       break;
     }
     // Leave the event loop when the lane-passes idled away by lanes that have dropped out of it
@@ -1298,24 +1228,11 @@ __launch_bounds__(kBlock, DDMC ? JB_DDMC_WAVES_PER_SIMD
     }
   }
 
-  if constexpr (TALLY) {
-    if (tally_in_lds) {
-      __syncthreads();  // every wave of the workgroup leaves the loop above exactly once
-      for (int q = threadIdx.x; q < M.nblocks * (int)M.ntot; q += blockDim.x) {
-        const double v = lds_tally[q];
-        if (v != 0.0) atomicAdd(&M.tally[q / (int)M.ntot][q % (int)M.ntot], v);
-      }
-    }
-  }
+  lds_tally_flush<TALLY>(M, lds_tally, tally_in_lds);
 
-  unsigned long long r_census = wave_sum(c_census), r_abs = wave_sum(c_abs), r_esc = wave_sum(c_esc),
-                     r_out = wave_sum(c_out), r_ev = c_ev;
+  done_c.flush<true>(counters, lane);
   if (lane == 0) {
-    if (r_census) atomicAdd(&counters[CNT_CENSUS], r_census);
-    if (r_abs) atomicAdd(&counters[CNT_ABSORBED], r_abs);
-    if (r_esc) atomicAdd(&counters[CNT_ESCAPED], r_esc);
-    if (r_out) atomicAdd(&counters[CNT_OUTGOING], r_out);
-    if (r_ev) atomicAdd(&counters[CNT_EVENTS], r_ev);
+    if (c_ev) atomicAdd(&counters[CNT_EVENTS], c_ev);
 #ifdef JB_TIMING
     atomicAdd(&counters[CNT_PASSES], cyc_ev >> 10);
     atomicAdd(&counters[CNT_SERVICE], cyc_sv >> 10);

@@ -314,19 +314,24 @@ def test_three_ways_to_step_agree_bit_for_bit(gpu_device, monkeypatch):
     _compare_ledger(a.md.ledger, want, 1e-12)
     la = _lib.EnergyLedger.from_dict(a.md.ledger)       # (the host sets the cycle of a ledger it closed itself)
     assert la.as_dict() == {k: v for k, v in a.md.ledger.items() if k not in ("e_start", "residual")}
-    # the C call
-    b, _ = _driver(cid, bset, gpu_device)
-    md = b.md
-    md._sync_stream()
-    e0 = _lib.EnergyLedger()
-    _lib.check(md.lib.jb_ledger_close(md.pkg.ctx, md.handle, C.byref(md.sv), 0.0, 0.0, C.byref(e0)))
-    next_id, cycle = C.c_uint64(md.next_id), C.c_uint32(md.cycle)
-    _lib.check(md.lib.jb_radiation_step(md.pkg.ctx, md.handle, C.byref(md.sv), 0.0, b.dt, C.byref(next_id),
-                                        C.byref(cycle), md.prefix.data_ptr()))
-    lb = _lib.EnergyLedger()
-    _lib.check(md.lib.jb_ledger_last(md.pkg.ctx, C.byref(lb)))
-    assert e0.e_census == a.md.ledger["e_start"]
+
+    def c_call():
+        b, _ = _driver(cid, bset, gpu_device)
+        md = b.md
+        md._sync_stream()
+        e0 = _lib.EnergyLedger()
+        _lib.check(md.lib.jb_ledger_close(md.pkg.ctx, md.handle, C.byref(md.sv), 0.0, 0.0, C.byref(e0)))
+        next_id, cycle = C.c_uint64(md.next_id), C.c_uint32(md.cycle)
+        _lib.check(md.lib.jb_radiation_step(md.pkg.ctx, md.handle, C.byref(md.sv), 0.0, b.dt, C.byref(next_id),
+                                            C.byref(cycle), md.prefix.data_ptr()))
+        lb = _lib.EnergyLedger()
+        _lib.check(md.lib.jb_ledger_last(md.pkg.ctx, C.byref(lb)))
+        assert e0.e_census == a.md.ledger["e_start"]
+        return lb, b
+
+    lb, b = c_call()
     # JB_HANDOFF=step on one rank
+    handoff_before = os.environ.get("JB_HANDOFF")
     monkeypatch.setenv("JB_HANDOFF", "step")
     c, _ = _driver(cid, bset, gpu_device)
     assert c.md.handoff == "step"
@@ -334,30 +339,48 @@ def test_three_ways_to_step_agree_bit_for_bit(gpu_device, monkeypatch):
     assert c.md.handoff_path().startswith("c: jb_radiation_step_ranks")
     lc_ = _lib.EnergyLedger()
     _lib.check(c.md.lib.jb_ledger_last(c.md.pkg.ctx, C.byref(lc_)))
+    if handoff_before is None:      # (further C calls run as the first one did)
+        monkeypatch.delenv("JB_HANDOFF")
+    else:
+        monkeypatch.setenv("JB_HANDOFF", handoff_before)
     sl = a.mesh.interior()
-    tally, slots = a.md.get_field("tally")[sl], a.md.get_swarm()["id"]
-    exact = 0
-    for name, other, drv in (("C call", lb, b), ("JB_HANDOFF=step", lc_, c)):
+
+    def inputs(drv):
+        return drv.md.get_field("tally")[sl], drv.md.get_swarm()["id"]
+
+    def agree(one, other):
         # Two of the ledger's INPUTS are not the same bits in every run of one problem: the tracking kernels
         # accumulate the tally field with atomics (tests/test_gpu_parity.py compares it to 1e-12 for that reason),
         # and RemoveMarkedParticles pairs holes with movers through an atomic cursor, so the slot ORDER of the census
         # swarm may differ (the existing tests compare swarms by creation id).  The ledger's sum of a given input is
         # reproducible (the sweep test above); here e_tally / e_census must be the same bits whenever the field /
         # the slot order is, and within 1e-12 otherwise.  Every other word of the struct must be identical.
-        same = {"e_tally": np.array_equal(tally, drv.md.get_field("tally")[sl]),
-                "e_census": np.array_equal(slots, drv.md.get_swarm()["id"])}
-        print(f"{name}: inputs bit-equal to the task path's: {same}")
+        (n1, l1, (tally1, slots1)), (n2, l2, (tally2, slots2)) = one, other
+        name = f"{n2} against {n1}"
+        same = {"e_tally": np.array_equal(tally1, tally2), "e_census": np.array_equal(slots1, slots2)}
+        print(f"{name}: inputs bit-equal: {same}")
         for k, _t in _lib.EnergyLedger._fields_:
-            x, y = getattr(la, k), getattr(other, k)
+            x, y = getattr(l1, k), getattr(l2, k)
             x, y = (list(x), list(y)) if hasattr(x, "__len__") else (x, y)
             if not same.get(k, True):
                 assert abs(x - y) <= 1e-12 * abs(y), (name, k, x, y)
             else:
                 assert x == y, (name, k, x, y)
         if all(same.values()):
-            assert bytes(la) == bytes(other), name
-        exact += sum(same.values())
-    # (the bit-equal branch must not go unused: if no input ever repeats, this says so)
+            assert bytes(l1) == bytes(l2), name
+        return sum(same.values())
+
+    runs = [("task path", la, inputs(a)), ("C call", lb, inputs(b)), ("JB_HANDOFF=step", lc_, inputs(c))]
+    exact = agree(runs[0], runs[1]) + agree(runs[0], runs[2]) + agree(runs[1], runs[2])
+    # (the bit-equal branch must not go unused.  Whether an input repeats is up to the order in which the hardware
+    # served the atomics -- in about half of the runs of these three neither does --, so the C call is made again,
+    # every run held against all earlier ones, until one repeats.)
+    for extra in range(64):
+        if exact > 0:
+            break
+        lx, x = c_call()
+        runs.append((f"C call {extra + 2}", lx, inputs(x)))
+        exact += sum(agree(r, runs[-1]) for r in runs[:-1])
     assert exact > 0, "neither the tally field nor the census slot order repeated in any of the runs"
 
 
