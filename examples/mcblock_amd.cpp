@@ -583,6 +583,12 @@ int main(int argc, char **argv) {
     md.comb_trigger = jb::CombTrigger(md.comb_target, pin.GetOrAddReal("jaybenne_amd", "census_comb_trigger", 2.0));
     // (as the Python driver: the order within a cell behind a sort -- any, or id: the canonical order)
     jb::SetCellOrder(&md, jb::CellOrderOf(pin.GetOrAddString("jaybenne_amd", "cell_order", "any")));
+    // (as the Python driver: deposition = exact -- energy_delta and the tally as one rounding of the exact sum;
+    // without the key the library's default, which JB_DEPOSITION sets)
+    {
+      const std::string dep = pin.GetOrAddString("jaybenne_amd", "deposition", "");
+      if (!dep.empty()) jb::SetDeposition(&md, jb::DepositionOf(dep));
+    }
     // (as the Python driver: the boundary source -- a black wall of temperature bsource_<face>_temperature behind a
     // domain face, bsource_num_particles photons per cycle over all such faces; every temperature 0 = off)
     md.bsource_num_particles = pin.GetOrAddInteger("jaybenne_amd", "bsource_num_particles", 0);

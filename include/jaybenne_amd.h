@@ -754,6 +754,82 @@ jb_status jb_ledger_reduce(jb_context *ctx, const jb_exchange_transport *transpo
  * JB_ERR_INVALID while the ledger is disabled or before the first close. */
 jb_status jb_ledger_last(const jb_context *ctx, jb_energy_ledger *out);
 
+/* ---- exact deposition: energy_delta and the census tally as ONE rounding of the exact sum of their addends --
+ * the same bits whatever the order of the photons, the launch geometry, the time of the last sort or the number
+ * of ranks (jaybenne_amd/csrc/jb_kernel_deposit.hpp, jb_deposit_fixed.hpp).  The reference has
+ * no such task.  JB_DEPOSIT_ATOMIC (the default): every tracking kernel adds an absorbed weight to energy_delta,
+ * and the fused tally a census weight to energy_tally, with a floating-point atomic; the last bit of a cell then
+ * depends on the order the adds arrive in, and with emission and feedback on it reaches the next cycle's
+ * opacities, emission counts and weights.  JB_DEPOSIT_EXACT:
+ *   - Per interior cell of every resident block the library keeps a 256-bit unsigned fixed-point accumulator
+ *     (four 64-bit words).  An addend w (finite, > 0) is converted at the cycle's scale exponent E: its 53-bit
+ *     significand is placed so that a weight of exponent E has its top bit at bit 222 -- 33 bits of headroom
+ *     above (2^32 addends of the largest weight, or heavier arrivals), and every addend of exponent >= E - 170
+ *     exact.  An addend with non-zero bits below is truncated, never rounded, and counted in n_truncated
+ *     (a function of (w, E) alone: the result stays independent of the order); w <= 0 or not finite adds nothing
+ *     and is counted in n_rejected, as is a slot whose block or cell indices lie outside a resident block.
+ *   - The adds are integer adds with carry (returning atomics: every wrap of a word is seen by exactly one).
+ *   - E is fixed for the cycle by the first accumulate call after a close: the largest exponent of w over slots
+ *     [0, swarm->n).  A later accumulate call of the cycle whose range [first, last) holds a heavier weight --
+ *     arrivals from a rank with hotter blocks can lie further above this rank's own weights than the headroom
+ *     reaches -- RAISES E to that weight's exponent in front of its sweep: every accumulator moves down by the
+ *     difference, and an accumulator that loses non-zero bits there is counted in n_truncated.  E is rank-local;
+ *     while n_truncated == 0 the sum is exact and does not depend on E, which is the condition the cross-rank
+ *     identity is stated under.
+ *   - After its launch every transport entry point sweeps exactly the range it followed and adds w of every
+ *     JB_ST_ABSORBED slot whose id has bit 63 clear to the cell (blk, kp, jp, ip) left in the slot; wherever
+ *     arrivals are unpacked (jb_unpack_incoming, jb_exchange) the arrivals are swept for JB_ST_ABSORBED slots WITH
+ *     bit 63.  Every deposit is counted once, by the rank that owns the cell.
+ *   - The tracking kernels and the unpack kernel are the ones of JB_DEPOSIT_ATOMIC, unchanged: they are handed a
+ *     mesh view whose energy_delta table points at a library-owned decoy field that nothing reads, so the real
+ *     fields never see an atomic.  fuse_census_tally is ignored (the plan is made without the tally); the tally is
+ *     the close's.
+ *   - jb_deposit_close, in this order: a set top bit in any accumulator of the absorbed sums (overflow) is
+ *     JB_ERR_INVALID before any field is written; energy_delta[q] = energy_delta[q] + D for every cell that received something, D the
+ *     accumulator as a double with one round-to-nearest-even; the accumulators zeroed; a new scale over the ACTIVE
+ *     slots; [0, swarm->n) swept for ACTIVE photons in owned blocks; energy_tally[q] = T / dv (dv = dx1 dx2 dx3 of
+ *     the block, cells without census photons 0); the accumulators zeroed again.  Two synchronisations.  A set top
+ *     bit after the census sweep is JB_ERR_INVALID too, before energy_tally is written but AFTER energy_delta has its
+ *     deposits.  Either error zeroes the accumulators: the sums of the stage that overflowed are lost with it.
+ *   - With accumulators open, jb_update_fluid and jb_ledger_close close them first (jb_update_fluid, which has no
+ *     swarm argument, with the swarm of the last accumulate, its n as jb_remove_marked_particles last left it): a
+ *     host that only flips the switch gets the right fields.  That view of the swarm is kept per mesh, with the
+ *     pointers of the last accumulate: a host that reallocates its swarm arrays between the last transport or
+ *     unpack call of a cycle and jb_update_fluid must call jb_deposit_close itself, with the new view.  jb_evaluate_radiation_energy computes the tally by
+ *     the exact path.  Changing the mode with accumulators open is JB_ERR_INVALID.
+ * Memory: 32 bytes of accumulator + 8 of decoy field per cell of the resident blocks, taken at the first use in
+ * EXACT mode: 40 B per cell, about 0.7 GB on a mesh of 256^3 cells.  JB_DEPOSITION=exact in the environment makes
+ * EXACT the default of jb_initialize, like JB_CELL_ORDER.  A replicated mesh sums its fields over the ranks in
+ * floating point: exact deposition is not for it. */
+enum { JB_DEPOSIT_ATOMIC = 0, JB_DEPOSIT_EXACT = 1 };
+enum { JB_DEPOSIT_ABSORBED = 1, JB_DEPOSIT_ARRIVALS = 2 };
+typedef struct jb_deposit_stats {
+  int64_t n_absorbed_addends;  /* addends of the absorbed and arrivals sweeps of the cycle the last close ended */
+  int64_t n_census_addends;    /* ... of its census sweep */
+  int64_t n_truncated;         /* addends of either with non-zero bits below the accumulator's bit 0 */
+  int64_t n_rejected;          /* slots of either that added nothing: w <= 0, not finite, or outside the mesh */
+  int32_t scale_absorbed;      /* E of the energy_delta stage (the biased exponent field of a double: 1 .. 2046) */
+  int32_t scale_census;        /* E of the tally stage */
+} jb_deposit_stats;
+jb_status jb_set_deposition(jb_context *ctx, int mode);
+int jb_get_deposition(const jb_context *ctx);
+/* The task form of the sweeps, for a host that unpacks with code of its own, and the tests: what = a sum of
+ * JB_DEPOSIT_ABSORBED (slots of [first, last) that are JB_ST_ABSORBED with bit 63 of the id clear) and
+ * JB_DEPOSIT_ARRIVALS (... with bit 63 set).  The contract of jb_ledger_accumulate: no slot twice, before any
+ * pack.  JB_ERR_INVALID in ATOMIC mode. */
+jb_status jb_deposit_accumulate(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, int64_t first,
+                                int64_t last, int what);
+jb_status jb_deposit_close(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm);
+/* The counts of the last close (synchronises the context's stream).  JB_ERR_INVALID in ATOMIC mode or before the
+ * first close. */
+jb_status jb_deposit_last(jb_context *ctx, jb_deposit_stats *out);
+/* What the mode has cost so far (diagnostics; no synchronisation): the device memory taken for this mesh's
+ * accumulators, decoy field and second view -- 0 until the mesh's first call in EXACT mode --, and the number of
+ * kernels of jb_kernel_deposit.hpp this context has launched -- it stands still in ATOMIC mode, and across a
+ * jb_update_fluid or jb_ledger_close that finds nothing open. */
+int64_t jb_deposit_memory(const jb_mesh *mesh);
+int64_t jb_deposit_kernel_launches(const jb_context *ctx);
+
 /* ---- transport invariants (checked library) -- the reference's PARTHENON_DEBUG_REQUIREs of the
  * tracking loop and of SampleDDMCBlockFace, evaluated on every pass (jaybenne_amd/csrc/jb_invariants.hpp).
  * `make -C jaybenne_amd/csrc checked` builds libjaybenne_amd_checked.so from the same sources with

@@ -677,6 +677,22 @@ inline int CellOrderOf(const std::string &value) {
   if (value == "id") return JB_CELL_ORDER_BY_ID;
   throw std::invalid_argument("jaybenne_amd/cell_order = '" + value + "': one of any, id");
 }
+// exact deposition: JB_DEPOSIT_ATOMIC (default) or JB_DEPOSIT_EXACT -- energy_delta and the census tally as one
+// rounding of the exact sum of their addends (jaybenne_amd.h: jb_set_deposition); DepositClose before UpdateFluid
+inline void SetDeposition(MeshData *md, int mode) { Check(jb_set_deposition(md->ctx(), mode)); }
+inline int GetDeposition(MeshData *md) { return jb_get_deposition(md->ctx()); }
+inline jb_deposit_stats DepositClose(MeshData *md) {
+  jb_deposit_stats s{};
+  Check(jb_deposit_close(md->ctx(), md->mesh(), &md->swarm));
+  Check(jb_deposit_last(md->ctx(), &s));
+  return s;
+}
+// the mode of the deck key <jaybenne_amd> deposition = atomic | exact
+inline int DepositionOf(const std::string &value) {
+  if (value == "atomic") return JB_DEPOSIT_ATOMIC;
+  if (value == "exact") return JB_DEPOSIT_EXACT;
+  throw std::invalid_argument("jaybenne_amd/deposition = '" + value + "': one of atomic, exact");
+}
 inline Real EstimateTimestepMesh(MeshData *md) { return jb_estimate_timestep(md->ctx()); }
 
 // jaybenne::InitializeRadiation(mbd, is_thermal) -- jaybenne.cpp:570-578
@@ -826,6 +842,8 @@ inline TaskStatus RadiationStep(MeshData *md, const Real t_start, const Real dt)
     Check(jb_remove_marked_particles(md->ctx(), &md->swarm));
   md->events += after.n_events - before.n_events;
   if (CheckCompletion(md, t_start + dt) != TaskStatus::complete) return TaskStatus::iterate;
+  // (exact deposition: energy_delta and the tally, each rounded once, before UpdateFluid reads them)
+  if (GetDeposition(md) == JB_DEPOSIT_EXACT) DepositClose(md);
   UpdateFluid(md);
   if (ledger) {
     jb_energy_ledger led{};

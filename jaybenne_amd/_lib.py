@@ -51,6 +51,8 @@ class Scattering(C.Structure):
 
 ARITH_EXACT, ARITH_LEAN = 0, 1   # enum of jb_set_arithmetic
 CELL_ORDER_ANY, CELL_ORDER_BY_ID = 0, 1   # enum of jb_set_cell_order
+DEPOSIT_ATOMIC, DEPOSIT_EXACT = 0, 1      # enum of jb_set_deposition
+JB_DEPOSIT_ABSORBED, JB_DEPOSIT_ARRIVALS = 1, 2   # what jb_deposit_accumulate sweeps for (a sum of them)
 
 FIELD_IDS = {"rho": 0, "sie": 1, "u": 2, "fleck": 3, "tally": 4, "edelta": 5}   # enum jb_field
 FIELD_NAMES = ("rho", "sie", "u", "fleck", "tally", "edelta", "src_ew", "src_num", "P1", "P2", "P3")
@@ -201,6 +203,15 @@ class CombReport(C.Structure):
     _fields_ = [("n_after", C.c_int64), ("n_new_ids", C.c_int64), ("e_after", C.c_double)]
 
 
+# jb_deposit_stats (include/jaybenne_amd.h): the counts of the last close of exact deposition
+class DepositStats(C.Structure):
+    _fields_ = [("n_absorbed_addends", C.c_int64), ("n_census_addends", C.c_int64), ("n_truncated", C.c_int64),
+                ("n_rejected", C.c_int64), ("scale_absorbed", C.c_int32), ("scale_census", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # jb_boundary_source_plan / jb_boundary_source_record (include/jaybenne_amd.h): the boundary source
 class BoundarySourcePlan(C.Structure):
     _fields_ = [("nper_block", C.c_void_p), ("e_face", C.c_double * 6), ("n_face", C.c_int64 * 6)]
@@ -292,6 +303,13 @@ PROTOTYPES = {
     "jb_get_arithmetic": (_int, [_vp]),
     "jb_set_cell_order": (_int, [_vp, _int]),
     "jb_get_cell_order": (_int, [_vp]),
+    "jb_set_deposition": (_int, [_vp, _int]),
+    "jb_get_deposition": (_int, [_vp]),
+    "jb_deposit_accumulate": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, _i64, _int]),
+    "jb_deposit_close": (_int, [_vp, _vp, C.POINTER(SwarmView)]),
+    "jb_deposit_last": (_int, [_vp, C.POINTER(DepositStats)]),
+    "jb_deposit_memory": (_i64, [_vp]),
+    "jb_deposit_kernel_launches": (_i64, [_vp]),
     "jb_debug_math": (_int, [_vp, _int, _vp, _int, _vp]),
     "jb_debug_model_coefficients": (_int, [_vp, C.POINTER(C.c_double * 4)]),
     "jb_debug_model_eval": (_int, [_vp, _int, _vp, _int, _vp]),

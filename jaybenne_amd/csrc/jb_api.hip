@@ -27,6 +27,7 @@
 #include "jb_kernel_comb.hpp"
 #include "jb_kernel_order.hpp"
 #include "jb_kernel_bsource.hpp"
+#include "jb_kernel_deposit.hpp"
 #include "jb_select.hpp"
 
 using namespace jb;
@@ -134,6 +135,12 @@ struct jb_context {
   char *bs_out_d = nullptr;            // [nblocks] counts, [nblocks][6] photons and energy of the last count call
   size_t bs_out_blocks = 0;
   jb_boundary_source_record bs_last{};
+  // exact deposition (jb_set_deposition; JB_DEPOSITION=exact at jb_initialize; jb_kernel_deposit.hpp): off by default
+  int deposition = JB_DEPOSIT_ATOMIC;
+  std::vector<jb_mesh *> dep_open_meshes;   // meshes of this context whose accumulators are open (a scale taken, no close yet)
+  long long dep_launches = 0;          // kernels of jb_kernel_deposit.hpp launched so far (jb_deposit_kernel_launches)
+  jb_deposit_stats dep_last{};
+  bool dep_has_last = false;
 };
 constexpr int kLedgerHead = 64;   // words in front of the partial sums (LW_N of them used)
 constexpr int kLedgerWords = (int)(sizeof(jb_energy_ledger) / 8);
@@ -178,7 +185,43 @@ struct jb_mesh {
   bool one_owner = true;
   // [nblocks][6]: 1 = face f of this owned block lies on the domain boundary (the boundary source's face cells)
   std::vector<uint8_t> bface_host;
+  // exact deposition, taken at the first use in that mode (deposit_ensure): the accumulators ([nblocks * ncell][4]
+  // words), their control words, and the view the tracking kernels get -- dm with the energy_delta table pointing
+  // at a decoy field nothing reads -- by value and in device memory
+  unsigned long long *dep_acc = nullptr, *dep_ctl = nullptr;
+  DevMesh dm_x{};
+  const DevMesh *dm_x_dev = nullptr;
+  bool dep_ready = false, dep_open = false;
+  size_t dep_bytes = 0;                // device memory taken for the above (jb_deposit_memory)
+  jb_swarm_view dep_swarm{};           // the swarm of this mesh's last accumulate: what jb_update_fluid closes with
 };
+// open / closed: the context knows the meshes whose accumulators are open (jb_set_deposition turns a change of mode
+// down while there is one, jb_remove_marked_particles keeps their swarm's n, jb_finalize lets go of them)
+static void deposit_mark_open(jb_context *ctx, jb_mesh *m) {
+  if (m->dep_open) return;
+  m->dep_open = true;
+  ctx->dep_open_meshes.push_back(m);
+}
+static void deposit_mark_closed(jb_context *ctx, jb_mesh *m) {
+  if (!m->dep_open) return;
+  m->dep_open = false;
+  for (size_t q = 0; q < ctx->dep_open_meshes.size(); ++q)
+    if (ctx->dep_open_meshes[q] == m) {
+      ctx->dep_open_meshes.erase(ctx->dep_open_meshes.begin() + (long)q);
+      break;
+    }
+}
+// the mesh view a tracking kernel (or k_unpack_incoming) is launched with
+static const DevMesh &track_dm(const jb_mesh *m) {
+  return m->ctx->deposition == JB_DEPOSIT_EXACT && m->dep_ready ? m->dm_x : m->dm;
+}
+static const DevMesh *track_dm_dev(const jb_mesh *m) {
+  return m->ctx->deposition == JB_DEPOSIT_EXACT && m->dep_ready ? m->dm_x_dev : m->dm_dev;
+}
+static jb_status deposit_ensure(jb_context *ctx, jb_mesh *mesh);
+static jb_status deposit_sweep(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, long long first,
+                               long long last, int what);
+static jb_status deposit_close(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm);
 
 __global__ void k_rcp_refined(double b, double *out) { *out = m_rcp_refined(b); }
 
@@ -436,6 +479,7 @@ extern "C" jb_status jb_initialize(const jb_params *params, const jb_eos *eos,
     ctx->lean_arith = !(ex && ex[0] == '1');
   }
   if (const char *e = getenv("JB_CELL_ORDER")) ctx->cell_order = strcmp(e, "id") == 0 ? JB_CELL_ORDER_BY_ID : JB_CELL_ORDER_ANY;
+  if (const char *e = getenv("JB_DEPOSITION")) ctx->deposition = strcmp(e, "exact") == 0 ? JB_DEPOSIT_EXACT : JB_DEPOSIT_ATOMIC;
   if (const char *e = getenv("JB_TRANSPORT_BLOCKS_PER_CU")) ctx->blocks_per_cu_env = atoi(e);
   if (const char *e = getenv("JB_NO_DDMC_ALL")) ctx->no_ddmc_all = e[0] == '1';
   if (const char *e = getenv("JB_NO_IMC_CELL")) ctx->no_imc_cell = e[0] == '1';
@@ -526,6 +570,9 @@ extern "C" jb_status jb_initialize(const jb_params *params, const jb_eos *eos,
 extern "C" jb_status jb_finalize(jb_context *ctx) {
   if (!ctx) return JB_COMPLETE;
   (void)hipSetDevice(ctx->device);
+  // (a mesh destroyed after its context must not look for it: its open accumulators are let go of here)
+  for (jb_mesh *m : ctx->dep_open_meshes) m->dep_open = false;
+  ctx->dep_open_meshes.clear();
   if (ctx->counters_d) (void)hipFree(ctx->counters_d);
   if (ctx->counters_h) (void)hipHostFree(ctx->counters_h);
   if (ctx->scratch_d) (void)hipFree(ctx->scratch_d);
@@ -894,6 +941,7 @@ extern "C" jb_status jb_mesh_create(jb_context *ctx, const jb_mesh_view *v, jb_m
 
 extern "C" jb_status jb_mesh_destroy(jb_mesh *m) {
   if (!m) return JB_COMPLETE;
+  if (m->dep_open) deposit_mark_closed(m->ctx, m);   // (dep_open: the context is alive, jb_finalize clears it)
   for (void *p : m->owned) (void)hipFree(p);
   delete m;
   return JB_COMPLETE;
@@ -1313,7 +1361,7 @@ static void launch_k_transport(jb_context *ctx, const jb_mesh *mesh, const Trans
       constexpr int G = decltype(gc)::value;
       const auto go = [&](auto dc, auto xc, auto lc) {
         launch_persistent<k_transport<NDIM, decltype(dc)::value, T, G, decltype(xc)::value, decltype(lc)::value>>(
-            ctx, last - first, 0, Occupancy::cached, mesh->dm, ctx->dp, S, t_start, dt, first, last,
+            ctx, last - first, 0, Occupancy::cached, track_dm(mesh), ctx->dp, S, t_start, dt, first, last,
             ctx->counters_d, (const int *)nullptr);
       };
       if constexpr (G != 0) {
@@ -1335,7 +1383,7 @@ static void launch_k_imc_cell(jb_context *ctx, const jb_mesh *mesh, const Transp
     with_bool(p.noabs, [&](auto nc) {
       with_bool(p.uniform, [&](auto uc) {
         launch_persistent<k_imc_cell<NDIM, decltype(tc)::value, decltype(nc)::value, decltype(uc)::value>>(
-            ctx, last - first, 0, Occupancy::cached, mesh->dm_dev, ctx->dp, S, t_start, dt, first, last,
+            ctx, last - first, 0, Occupancy::cached, track_dm_dev(mesh), ctx->dp, S, t_start, dt, first, last,
             ctx->counters_d, mesh->nbr_dq);
       });
     });
@@ -1363,7 +1411,7 @@ static void launch_k_hybrid(jb_context *ctx, const jb_mesh *mesh, const Transpor
         constexpr bool T = decltype(tc)::value, NA = decltype(nc)::value;
         constexpr int MD = decltype(mc)::value;
         const auto go = [&](auto kc) {
-          launch_persistent<decltype(kc)::value>(ctx, l - f, 0, policy, mesh->dm_dev, ctx->dp, S, t_start, dt, f, l,
+          launch_persistent<decltype(kc)::value>(ctx, l - f, 0, policy, track_dm_dev(mesh), ctx->dp, S, t_start, dt, f, l,
                                                  ctx->counters_d, list_in, list_out, count_out, count_in);
         };
         if constexpr (NA && MD == 0) {
@@ -1393,7 +1441,7 @@ static jb_status launch_all_ddmc(jb_context *ctx, const jb_mesh *mesh, const Tra
     const auto go = [&](auto kc) {
       launch_persistent<decltype(kc)::value>(ctx, last - first, p.dyn_lds,
                                              p.occ_cap3 ? Occupancy::per_launch_cap3 : Occupancy::per_launch,
-                                             mesh->dm_dev, ctx->dp, S, t_start, dt, first, last, ctx->counters_d,
+                                             track_dm_dev(mesh), ctx->dp, S, t_start, dt, first, last, ctx->counters_d,
                                              (const int *)mesh->dm.not_all_ddmc, handed, n_handed);
     };
     if (p.family == Family::k_ddmc_q)
@@ -1500,9 +1548,13 @@ static jb_status transport_impl(jb_context *ctx, jb_mesh *mesh, const jb_swarm_v
   const DevMesh &M = mesh->dm;
   if (ddmc && (!M.P1 || (M.ndim > 1 && !M.P2) || (M.ndim > 2 && !M.P3)))
     return fail(JB_ERR_INVALID, "DDMC transport needs the ddmc_face_prob arrays");
+  // (exact deposition: the tracking kernels deposit into the decoy field, the plan is made without the tally; the
+  // decoy view exists from the first call in this mode on, whatever its range)
+  const bool exact_dep = ctx->deposition == JB_DEPOSIT_EXACT;
+  if (exact_dep && (st = deposit_ensure(ctx, mesh)) != JB_COMPLETE) return st;
   if (first == last) return JB_COMPLETE;
   const DevSwarm S = dev_swarm(swarm);
-  const bool tl = tally != 0;
+  const bool tl = tally != 0 && !exact_dep;
 #ifdef JB_INVARIANTS
   st = inv_sweep(ctx, M, S, first, last, t_start + dt, false);   // (checked build) SWARM on entry (k_inv_swarm)
   if (st != JB_COMPLETE) return st;
@@ -1527,6 +1579,8 @@ static jb_status transport_impl(jb_context *ctx, jb_mesh *mesh, const jb_swarm_v
   if (ev_stop) (void)hipEventRecord(ev_stop, ctx->stream);
   if (st != JB_COMPLETE) return st;
   JB_HIP(hipGetLastError());
+  // (exact deposition: exactly the range this call followed, before any pack turns packed slots into holes)
+  if (exact_dep) return deposit_sweep(ctx, mesh, swarm, first, last, DEP_ABSORBED);
   return JB_COMPLETE;
 }
 
@@ -1595,6 +1649,19 @@ extern "C" jb_status jb_set_cell_order(jb_context *ctx, int mode) {
 }
 extern "C" int jb_get_cell_order(const jb_context *ctx) {
   return ctx && ctx->cell_order == JB_CELL_ORDER_BY_ID ? JB_CELL_ORDER_BY_ID : JB_CELL_ORDER_ANY;
+}
+
+extern "C" jb_status jb_set_deposition(jb_context *ctx, int mode) {
+  if (!ctx || (mode != JB_DEPOSIT_ATOMIC && mode != JB_DEPOSIT_EXACT))
+    return fail(JB_ERR_INVALID, "jb_set_deposition: mode = %d is neither JB_DEPOSIT_ATOMIC nor JB_DEPOSIT_EXACT", mode);
+  if (mode != ctx->deposition && !ctx->dep_open_meshes.empty())
+    return fail(JB_ERR_INVALID, "jb_set_deposition: accumulators are open (jb_deposit_close first)");
+  if (mode != ctx->deposition) ctx->dep_has_last = false;
+  ctx->deposition = mode;
+  return JB_COMPLETE;
+}
+extern "C" int jb_get_deposition(const jb_context *ctx) {
+  return ctx && ctx->deposition == JB_DEPOSIT_EXACT ? JB_DEPOSIT_EXACT : JB_DEPOSIT_ATOMIC;
 }
 
 static jb_status fetch_counters(jb_context *ctx) {
@@ -1699,6 +1766,8 @@ extern "C" jb_status jb_evaluate_radiation_energy(jb_context *ctx, jb_mesh *mesh
   if (st != JB_COMPLETE) return st;
   st = check_swarm(swarm, "jb_evaluate_radiation_energy");
   if (st != JB_COMPLETE) return st;
+  // (exact deposition: the tally by the exact path -- the close, which also lands what is open of energy_delta)
+  if (ctx->deposition == JB_DEPOSIT_EXACT) return deposit_close(ctx, mesh, swarm);
   if (swarm->n > 0)
     hipLaunchKernelGGL(k_tally, dim3(grid_for(ctx, swarm->n)), dim3(kBlock), 0, ctx->stream, mesh->dm,
                        dev_swarm(swarm), (long long)swarm->n);
@@ -1710,6 +1779,11 @@ extern "C" jb_status jb_update_fluid(jb_context *ctx, jb_mesh *mesh) {
   JB_RANGE("Jaybenne::UpdateFluid");
   if (!ctx || !mesh) return fail(JB_ERR_INVALID, "null argument");
   JB_HIP(hipSetDevice(ctx->device));
+  // (exact deposition: with accumulators open the close comes first, so that energy_delta is final)
+  if (mesh->dep_open) {
+    const jb_status st = deposit_close(ctx, mesh, &mesh->dep_swarm);
+    if (st != JB_COMPLETE) return st;
+  }
   if (!ctx->params.do_feedback) return JB_COMPLETE;  // jaybenne.cpp:590
   const DevMesh &M = mesh->dm;
   hipLaunchKernelGGL(k_update_fluid, dim3(grid_for(ctx, (long long)M.nblocks * M.ncell)), dim3(kBlock), 0,
@@ -1768,6 +1842,8 @@ extern "C" jb_status jb_remove_marked_particles(jb_context *ctx, jb_swarm_view *
     JB_HIP(hipGetLastError());
   }
   swarm->n = survivors;
+  for (jb_mesh *m : ctx->dep_open_meshes)   // (what jb_update_fluid closes with)
+    if (m->dep_swarm.x == swarm->x) m->dep_swarm.n = survivors;
   return JB_COMPLETE;
 }
 
@@ -2320,8 +2396,10 @@ extern "C" jb_status jb_unpack_incoming(jb_context *ctx, jb_mesh *mesh, jb_swarm
   if (swarm->n + nrecords > swarm->capacity)
     return fail(JB_ERR_CAPACITY, "swarm capacity %lld too small for %lld arrivals",
                 (long long)swarm->capacity, (long long)nrecords);
+  // (exact deposition: the decoy view must exist BEFORE the launch, also when this is the mesh's first call in the mode)
+  if (ctx->deposition == JB_DEPOSIT_EXACT && (st = deposit_ensure(ctx, mesh)) != JB_COMPLETE) return st;
   hipLaunchKernelGGL(k_unpack_incoming, dim3(grid_for(ctx, nrecords)), dim3(kBlock), 0, ctx->stream,
-                     mesh->dm, dev_swarm(swarm), (long long)swarm->n, (const long long *)records_dev,
+                     track_dm(mesh), dev_swarm(swarm), (long long)swarm->n, (const long long *)records_dev,
                      (long long)nrecords);
   JB_HIP(hipGetLastError());
 #ifdef JB_INVARIANTS
@@ -2331,6 +2409,9 @@ extern "C" jb_status jb_unpack_incoming(jb_context *ctx, jb_mesh *mesh, jb_swarm
   }
 #endif
   swarm->n += nrecords;
+  // (exact deposition: the arrivals absorbed in a halo copy on their sender, deposited here by the owner)
+  if (ctx->deposition == JB_DEPOSIT_EXACT)
+    return deposit_sweep(ctx, mesh, swarm, swarm->n - nrecords, swarm->n, DEP_ARRIVALS);
   return JB_COMPLETE;
 }
 
@@ -2376,6 +2457,9 @@ extern "C" jb_status jb_exchange(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *
   if (nranks < mesh->nranks_seen || nranks + kRoomWords > kRankEnd - kRankBase)
     return fail(JB_ERR_INVALID, "nranks = %d does not cover the owners in the mesh view", nranks);
   *nsent = 0; *nreceived = 0; *moved_anywhere = 0;
+  // (exact deposition: the decoy view k_unpack_incoming gets must exist before its launch, also when the exchange is
+  // this mesh's first call in the mode -- a rank whose swarm was empty so far; taken here, in front of the collectives)
+  if (ctx->deposition == JB_DEPOSIT_EXACT && (st = deposit_ensure(ctx, mesh)) != JB_COMPLETE) return st;
   const int row = nranks + kRoomWords;   // what a rank contributes to the all-gather: counts | send, receive, swarm room
   // 1. records per destination rank, counted on the device ...
   unsigned long long *per_rank = ctx->counters_d + kRankBase;
@@ -2473,7 +2557,7 @@ extern "C" jb_status jb_exchange(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *
     return fail(JB_ERR_HIP, "jb_exchange: the transport's record exchange failed");
   if (mine_in > 0) {
     hipLaunchKernelGGL(k_unpack_incoming, dim3(grid_for(ctx, mine_in)), dim3(kBlock), 0, ctx->stream,
-                       mesh->dm, dev_swarm(swarm), (long long)swarm->n, (const long long *)recv_dev,
+                       track_dm(mesh), dev_swarm(swarm), (long long)swarm->n, (const long long *)recv_dev,
                        (long long)mine_in);
     JB_HIP(hipGetLastError());
 #ifdef JB_INVARIANTS
@@ -2482,6 +2566,8 @@ extern "C" jb_status jb_exchange(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *
       return JB_ERR_HIP;
 #endif
     swarm->n += mine_in;
+    if (ctx->deposition == JB_DEPOSIT_EXACT)
+      return deposit_sweep(ctx, mesh, swarm, swarm->n - mine_in, swarm->n, DEP_ARRIVALS);
   }
   return JB_COMPLETE;
 }
@@ -2678,6 +2764,11 @@ extern "C" jb_status jb_ledger_accumulate(jb_context *ctx, jb_mesh *mesh, const 
 static jb_status ledger_close(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, double t_start, double dt,
                               long long cycle, jb_energy_ledger *out) {
   const DevMesh &M = mesh->dm;
+  // (exact deposition: e_delta and e_tally read final fields)
+  if (mesh->dep_open) {
+    const jb_status dst = deposit_close(ctx, mesh, swarm);
+    if (dst != JB_COMPLETE) return dst;
+  }
   jb_status st = ledger_sweep(ctx, M, dev_swarm(swarm), 0, swarm->n, LEDGER_CENSUS);
   if (st != JB_COMPLETE) return st;
   {
@@ -2786,6 +2877,200 @@ extern "C" jb_status jb_ledger_last(const jb_context *ctx, jb_energy_ledger *out
 }
 
 // ------------------------------------------------------------------------------------------------
+// Exact deposition (include/jaybenne_amd.h: jb_set_deposition; jb_kernel_deposit.hpp).
+
+// (every launch of a kernel of jb_kernel_deposit.hpp is counted: jb_deposit_kernel_launches)
+#define JB_DEP_LAUNCH(ctx, ...)          \
+  do {                                   \
+    hipLaunchKernelGGL(__VA_ARGS__);     \
+    ++(ctx)->dep_launches;               \
+  } while (0)
+
+// the accumulators, their control words, the decoy energy_delta field and the view that names it: once per mesh
+static jb_status deposit_ensure(jb_context *ctx, jb_mesh *mesh) {
+  if (mesh->dep_ready) return JB_COMPLETE;
+  const DevMesh &M = mesh->dm;
+  const size_t cells = (size_t)M.nblocks * (size_t)M.ncell, per = (size_t)M.ntot;
+  unsigned long long *acc = nullptr;
+  double *decoy = nullptr;
+  JB_HIP(hipMalloc(&acc, (cells * kDepWords + DC_N) * sizeof(unsigned long long)));
+  mesh->owned.push_back(acc);
+  JB_HIP(hipMalloc(&decoy, sizeof(double) * per * (size_t)M.nblocks));
+  mesh->owned.push_back(decoy);
+  JB_HIP(hipMemsetAsync(acc, 0, (cells * kDepWords + DC_N) * sizeof(unsigned long long), ctx->stream));
+  JB_HIP(hipMemsetAsync(decoy, 0, sizeof(double) * per * (size_t)M.nblocks, ctx->stream));
+  std::vector<const double *> tab((size_t)M.nblocks);
+  for (int b = 0; b < M.nblocks; ++b) tab[(size_t)b] = decoy + (size_t)b * per;
+  const double *const *tab_d = nullptr;
+  jb_status st = upload(mesh, (const double *const *)tab.data(), (size_t)M.nblocks, &tab_d);
+  if (st != JB_COMPLETE) return st;
+  mesh->dm_x = mesh->dm;
+  mesh->dm_x.edelta = (double *const *)tab_d;
+  const DevMesh *copy = nullptr;
+  if ((st = upload(mesh, &mesh->dm_x, 1, &copy)) != JB_COMPLETE) return st;
+  mesh->dm_x_dev = copy;
+  mesh->dep_acc = acc;
+  mesh->dep_ctl = acc + cells * kDepWords;
+  mesh->dep_ready = true;
+  mesh->dep_bytes = (cells * kDepWords + DC_N) * sizeof(unsigned long long) + sizeof(double) * per * (size_t)M.nblocks +
+                    sizeof(double *) * (size_t)M.nblocks + sizeof(DevMesh);
+  return JB_COMPLETE;
+}
+
+static int deposit_grid(const jb_context *ctx, long long n) {
+  const long long tile = (long long)kLedgerUnroll * kBlock;
+  long long blocks = (n + tile - 1) / tile;
+  const long long cap = (long long)ctx->num_cu * 8;
+  return (int)(blocks > cap ? cap : (blocks < 1 ? 1 : blocks));
+}
+
+template <int WHAT>
+static void launch_deposit_sweep(jb_context *ctx, const jb_mesh *mesh, const DevSwarm &S, long long first,
+                                 long long last) {
+  const DevMesh &M = mesh->dm;
+  const dim3 grid((unsigned)deposit_grid(ctx, last - first)), block(kBlock);
+  if ((long long)M.nblocks * M.ncell <= (long long)kDepositLds)
+    JB_DEP_LAUNCH(ctx, (k_deposit_sweep<WHAT, true>), grid, block, 0, ctx->stream, M, S, first, last, mesh->dep_acc,
+                       mesh->dep_ctl);
+  else
+    JB_DEP_LAUNCH(ctx, (k_deposit_sweep<WHAT, false>), grid, block, 0, ctx->stream, M, S, first, last, mesh->dep_acc,
+                       mesh->dep_ctl);
+}
+
+// One sweep of [first, last) into the mesh's accumulators; the first one after a close takes the cycle's scale
+// over [0, swarm->n) in front of it.
+static jb_status deposit_sweep(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, long long first,
+                               long long last, int what) {
+  jb_status st = deposit_ensure(ctx, mesh);
+  if (st != JB_COMPLETE) return st;
+  const DevSwarm S = dev_swarm(swarm);
+  mesh->dep_swarm = *swarm;
+  if (!mesh->dep_open) {
+    JB_HIP(hipMemsetAsync(mesh->dep_ctl, 0, DC_N * sizeof(unsigned long long), ctx->stream));
+    if (swarm->n > 0)
+      JB_DEP_LAUNCH(ctx, k_deposit_scale<false>, dim3(deposit_grid(ctx, swarm->n)), dim3(kBlock), 0, ctx->stream, S,
+                         0ll, (long long)swarm->n, mesh->dep_ctl, (int)DC_SCALE);
+    deposit_mark_open(ctx, mesh);
+  } else if (last > first) {
+    // (a later sweep of the cycle: a heavier weight in its range raises the scale, jb_kernel_deposit.hpp)
+    const DevMesh &M = mesh->dm;
+    const long long cells = (long long)M.nblocks * M.ncell;
+    JB_DEP_LAUNCH(ctx, k_deposit_scale<false>, dim3(deposit_grid(ctx, last - first)), dim3(kBlock), 0, ctx->stream, S,
+                       first, last, mesh->dep_ctl, (int)DC_SCALE_NEW);
+    JB_DEP_LAUNCH(ctx, k_deposit_rescale, dim3(grid_for(ctx, cells)), dim3(kBlock), 0, ctx->stream, cells, mesh->dep_acc,
+                       mesh->dep_ctl);
+    JB_DEP_LAUNCH(ctx, k_deposit_commit, dim3(1), dim3(1), 0, ctx->stream, mesh->dep_ctl);
+  }
+  if (last > first) {
+    switch (what) {
+    case DEP_ABSORBED: launch_deposit_sweep<DEP_ABSORBED>(ctx, mesh, S, first, last); break;
+    case DEP_ARRIVALS: launch_deposit_sweep<DEP_ARRIVALS>(ctx, mesh, S, first, last); break;
+    default: launch_deposit_sweep<DEP_BOTH>(ctx, mesh, S, first, last); break;
+    }
+  }
+  JB_HIP(hipGetLastError());
+  return JB_COMPLETE;
+}
+
+// the control words on the host (one synchronisation); a set top bit is the overflow of an accumulator
+static jb_status deposit_read_ctl(jb_context *ctx, jb_mesh *mesh, unsigned long long (&ctl)[DC_N], const char *stage) {
+  JB_HIP(hipMemcpyAsync(ctl, mesh->dep_ctl, sizeof ctl, hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  if (ctl[DC_TOP_BIT] != 0) {
+    // (nothing of THIS stage has been written to a field -- an overflow of the census stage comes after energy_delta
+    // has its deposits --; the accumulators start over: the stage's sums are lost with the error)
+    const size_t cells = (size_t)mesh->dm.nblocks * (size_t)mesh->dm.ncell;
+    (void)hipMemsetAsync(mesh->dep_acc, 0, (cells * kDepWords + DC_N) * sizeof(unsigned long long), ctx->stream);
+    deposit_mark_closed(ctx, mesh);
+    return fail(JB_ERR_INVALID, "jb_deposit_close: an accumulator of the %s stage overflowed (%llu adds reached the top bit)",
+                stage, ctl[DC_TOP_BIT]);
+  }
+  return JB_COMPLETE;
+}
+
+static jb_status deposit_close(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm) {
+  jb_status st = deposit_ensure(ctx, mesh);
+  if (st != JB_COMPLETE) return st;
+  const DevMesh &M = mesh->dm;
+  const DevSwarm S = dev_swarm(swarm);
+  const dim3 cgrid((unsigned)grid_for(ctx, (long long)M.nblocks * M.ncell)), block(kBlock);
+  unsigned long long ctl[DC_N] = {};
+  jb_deposit_stats stats{};
+  // 1. what the cycle absorbed, into energy_delta
+  if (mesh->dep_open) {
+    if ((st = deposit_read_ctl(ctx, mesh, ctl, "energy_delta")) != JB_COMPLETE) return st;
+    const int E = ctl[DC_SCALE] != 0 ? (int)ctl[DC_SCALE] : 1;
+    stats.n_absorbed_addends = (int64_t)ctl[DC_N_ABSORBED];
+    stats.n_truncated = (int64_t)ctl[DC_N_TRUNCATED];
+    stats.n_rejected = (int64_t)ctl[DC_N_REJECTED];
+    stats.scale_absorbed = E;
+    if (ctl[DC_N_ABSORBED] != 0)
+      JB_DEP_LAUNCH(ctx, k_deposit_final<0>, cgrid, block, 0, ctx->stream, M, mesh->dep_acc, E);
+    deposit_mark_closed(ctx, mesh);
+  }
+  // 2. the census, through the same accumulators (zero again), into energy_tally
+  JB_HIP(hipMemsetAsync(mesh->dep_ctl, 0, DC_N * sizeof(unsigned long long), ctx->stream));
+  if (swarm->n > 0) {
+    JB_DEP_LAUNCH(ctx, k_deposit_scale<true>, dim3(deposit_grid(ctx, swarm->n)), block, 0, ctx->stream, S, 0ll,
+                       (long long)swarm->n, mesh->dep_ctl, (int)DC_SCALE);
+    launch_deposit_sweep<DEP_CENSUS>(ctx, mesh, S, 0, swarm->n);
+  }
+  JB_HIP(hipGetLastError());
+  if ((st = deposit_read_ctl(ctx, mesh, ctl, "energy_tally")) != JB_COMPLETE) return st;
+  const int Et = ctl[DC_SCALE] != 0 ? (int)ctl[DC_SCALE] : 1;
+  JB_DEP_LAUNCH(ctx, k_deposit_final<1>, cgrid, block, 0, ctx->stream, M, mesh->dep_acc, Et);
+  JB_HIP(hipGetLastError());
+  stats.n_census_addends = (int64_t)ctl[DC_N_CENSUS];
+  stats.n_truncated += (int64_t)ctl[DC_N_TRUNCATED];
+  stats.n_rejected += (int64_t)ctl[DC_N_REJECTED];
+  stats.scale_census = Et;
+  ctx->dep_last = stats;
+  ctx->dep_has_last = true;
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_deposit_accumulate(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, int64_t first,
+                                           int64_t last, int what) {
+  if (!ctx || !mesh || !swarm) return fail(JB_ERR_INVALID, "jb_deposit_accumulate: null argument");
+  if (ctx->deposition != JB_DEPOSIT_EXACT)
+    return fail(JB_ERR_INVALID, "jb_deposit_accumulate: deposition is not exact (jb_set_deposition)");
+  if (what < JB_DEPOSIT_ABSORBED || what > (JB_DEPOSIT_ABSORBED | JB_DEPOSIT_ARRIVALS))
+    return fail(JB_ERR_INVALID, "jb_deposit_accumulate: what = %d is no sum of JB_DEPOSIT_ABSORBED and JB_DEPOSIT_ARRIVALS", what);
+  JB_HIP(hipSetDevice(ctx->device));
+  const jb_status st = check_swarm(swarm, "jb_deposit_accumulate");
+  if (st != JB_COMPLETE) return st;
+  if (first < 0 || last > swarm->n || first > last)
+    return fail(JB_ERR_INVALID, "jb_deposit_accumulate: particle range [%lld,%lld) outside the swarm (n = %lld)",
+                (long long)first, (long long)last, (long long)swarm->n);
+  static_assert(JB_DEPOSIT_ABSORBED == DEP_ABSORBED && JB_DEPOSIT_ARRIVALS == DEP_ARRIVALS && DEP_BOTH == 3, "");
+  return deposit_sweep(ctx, mesh, swarm, first, last, what);
+}
+
+extern "C" jb_status jb_deposit_close(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm) {
+  if (!ctx || !mesh || !swarm) return fail(JB_ERR_INVALID, "jb_deposit_close: null argument");
+  if (ctx->deposition != JB_DEPOSIT_EXACT)
+    return fail(JB_ERR_INVALID, "jb_deposit_close: deposition is not exact (jb_set_deposition)");
+  JB_HIP(hipSetDevice(ctx->device));
+  const jb_status st = check_swarm(swarm, "jb_deposit_close");
+  if (st != JB_COMPLETE) return st;
+  return deposit_close(ctx, mesh, swarm);
+}
+
+extern "C" int64_t jb_deposit_memory(const jb_mesh *mesh) { return mesh ? (int64_t)mesh->dep_bytes : 0; }
+extern "C" int64_t jb_deposit_kernel_launches(const jb_context *ctx) { return ctx ? (int64_t)ctx->dep_launches : 0; }
+
+extern "C" jb_status jb_deposit_last(jb_context *ctx, jb_deposit_stats *out) {
+  if (!ctx || !out) return fail(JB_ERR_INVALID, "jb_deposit_last: null argument");
+  if (ctx->deposition != JB_DEPOSIT_EXACT)
+    return fail(JB_ERR_INVALID, "jb_deposit_last: deposition is not exact (jb_set_deposition)");
+  if (!ctx->dep_has_last) return fail(JB_ERR_INVALID, "jb_deposit_last: no close yet");
+  JB_HIP(hipSetDevice(ctx->device));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  *out = ctx->dep_last;
+  return JB_COMPLETE;
+}
+
+// ------------------------------------------------------------------------------------------------
 // RadiationStep for a mesh held entirely by this rank: the task list of jaybenne.cpp:104-138 with
 // the iterate-sublist collapsed to one launch (every block crossing is resolved in flight).
 static jb_status radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, double t_start, double dt,
@@ -2870,6 +3155,7 @@ static jb_status radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *s
     st = jb_remove_marked_particles(ctx, swarm);
     if (st != JB_COMPLETE) return st;
   }
+  if (ctx->deposition == JB_DEPOSIT_EXACT && (st = deposit_close(ctx, mesh, swarm)) != JB_COMPLETE) return st;
   st = jb_update_fluid(ctx, mesh);
   if (st != JB_COMPLETE || !ctx->ledger_on) return st;
   return ledger_close(ctx, mesh, swarm, t_start, dt, (long long)*cycle, nullptr);
@@ -3115,6 +3401,8 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
       after.n_outgoing != before.n_outgoing) {
     if ((st = jb_remove_marked_particles(ctx, swarm)) != JB_COMPLETE) return done(st);
   }
+  // (exact deposition: the close is local to the rank, no collective)
+  if (ctx->deposition == JB_DEPOSIT_EXACT && (st = deposit_close(ctx, mesh, swarm)) != JB_COMPLETE) return done(st);
   st = jb_update_fluid(ctx, mesh);
   if (st != JB_COMPLETE || !ctx->ledger_on) return done(st);
   // the close, and one more all-gather made on every rank (the ledger is on on all of them or on none)

@@ -12,6 +12,9 @@ constexpr int kLdsBlocks = JB_LDS_BLOCKS;
 constexpr int kQBlocks = 64;   // ... of k_ddmc_q (k_ddmc_all: 128): with the queues the workgroup stays under
                                // 40 KB of LDS, i.e. four workgroups per CU
 constexpr int kLdsTally = 1024;  // cells (all resident blocks, ghosts included) tallied in LDS
+// interior cells (all resident blocks) whose 256-bit deposition accumulators a sweep keeps in LDS
+// (jb_kernel_deposit.hpp): 32 bytes per cell, 32 KB per workgroup -- five workgroups per CU still fit
+constexpr int kDepositLds = kLdsTally;
 // cell codes of the all-DDMC kernel (DevMesh::ddmc_code)
 constexpr int kMaxClasses = 256;            // 16 KB of LDS per workgroup at most
 constexpr int kLdsRecCells = 256;    // cells whose step records k_ddmc_all<.., GATHER 2> copies to LDS (jb_kernel_ddmc.hpp)

@@ -262,6 +262,9 @@ class MeshData:
         self.comb_trigger = 0
         self.comb_history: list = []                # one dict per cycle whose comb changed the swarm
         self._comb_sorted = False                   # the last plan sorted the swarm
+        # exact deposition (md.deposition; include/jaybenne_amd.h: jb_set_deposition): one record per cycle, the
+        # counts of its close on this rank (jb_deposit_stats) and the cycle
+        self.deposit_history: list = []
         # boundary source (SetBoundarySource; include/jaybenne_amd.h: jb_source_boundary_count): Planckian inflow
         # through the domain faces that carry a temperature; every face off (the default) = the reference
         self.bsource_num_particles = 0              # N_b: photons per cycle over all source faces of the whole mesh
@@ -424,6 +427,32 @@ class MeshData:
     @cell_order.setter
     def cell_order(self, mode: str) -> None:
         _lib.check(self.lib.jb_set_cell_order(self.pkg.ctx, cell_order_code(mode)))
+
+    # ---- exact deposition
+    @property
+    def deposition(self) -> str:
+        """``"atomic"`` (the default) or ``"exact"``: energy_delta and the census tally as one rounding of the exact
+        sum of their addends -- the same bits whatever the order of the photons, the time of the last sort or the
+        number of ranks (include/jaybenne_amd.h: ``jb_set_deposition``).  Every cycle then appends the counts of its
+        close to ``md.deposit_history``."""
+        return DEPOSITIONS[self.lib.jb_get_deposition(self.pkg.ctx)]
+
+    @deposition.setter
+    def deposition(self, mode: str) -> None:
+        if mode == "exact" and self.replicated:
+            raise ValueError("deposition = 'exact': a replicated mesh sums its fields over the ranks in floating point")
+        _lib.check(self.lib.jb_set_deposition(self.pkg.ctx, deposition_code(mode)))
+
+    def deposit_close(self) -> dict:
+        """``jb_deposit_close`` on this rank's swarm, then the counts of that close (``jb_deposit_last``)."""
+        self._sync_stream()
+        _lib.check(self.lib.jb_deposit_close(self.pkg.ctx, self.handle, C.byref(self.sv)))
+        return self.deposit_last()
+
+    def deposit_last(self) -> dict:
+        st = _lib.DepositStats()
+        _lib.check(self.lib.jb_deposit_last(self.pkg.ctx, C.byref(st)))
+        return st.as_dict()
 
     def _ledger_transport(self):
         """The jb_exchange_transport the ledgers of several ranks are gathered through."""
@@ -781,6 +810,15 @@ def DefragParticles(md: MeshData) -> TaskStatus:
 
 
 CELL_ORDERS = ("any", "id")
+DEPOSITIONS = ("atomic", "exact")
+
+
+def deposition_code(mode: str, key: str = "deposition") -> int:
+    """``JB_DEPOSIT_ATOMIC`` / ``_EXACT`` of ``atomic`` / ``exact`` (the values of the deck key
+    ``<jaybenne_amd> deposition``); anything else is an error that names ``key``."""
+    if mode not in DEPOSITIONS:
+        raise ValueError(f"{key} = {mode!r}: one of atomic, exact")
+    return DEPOSITIONS.index(mode)
 
 
 def cell_order_code(mode: str, key: str = "cell_order") -> int:
@@ -1013,6 +1051,8 @@ def _radiation_step_ranks(md: MeshData, t_start: float, dt: float) -> TaskStatus
         last = _lib.BoundarySourceRecord()
         _lib.check(md.lib.jb_boundary_source_last(pkg.ctx, C.byref(last)))
         _record_boundary_source(md, dict(e_face=list(last.e_face), n_face=list(last.n_face)))
+    if md.deposition == "exact":   # (closed inside the call, before UpdateFluid)
+        md.deposit_history.append(dict(md.deposit_last(), cycle=md.cycle))
     if ledger:     # (closed and reduced over the ranks inside the call)
         led = _lib.EnergyLedger()
         _lib.check(md.lib.jb_ledger_last(pkg.ctx, C.byref(led)))
@@ -1103,6 +1143,8 @@ def _radiation_step(md: MeshData, t_start: float, dt: float) -> TaskStatus:
         if any(after[k] != before[k] for k in ("n_absorbed", "n_escaped", "n_outgoing")):
             RemoveMarkedParticles(md)
         md.events += after["n_events"] - before["n_events"]
+        if md.deposition == "exact":     # energy_delta and the tally, each rounded once, before UpdateFluid reads them
+            md.deposit_history.append(dict(md.deposit_close(), cycle=md.cycle))
         UpdateFluid(md)
         if ledger:
             led = _lib.EnergyLedger()

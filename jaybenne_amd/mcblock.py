@@ -256,6 +256,17 @@ def deck_cell_order(pin: ParameterInput) -> str:
     return mode
 
 
+def deck_deposition(pin: ParameterInput) -> str:
+    """``<jaybenne_amd> deposition = atomic | exact``; without the key ``None`` (the library's default, which
+    JB_DEPOSITION sets); anything else raises with the key named."""
+    mode = pin.GetOrAddString("jaybenne_amd", "deposition", "").strip()
+    if mode == "":
+        return None
+    if mode not in ("atomic", "exact"):
+        raise ValueError(f"jaybenne_amd/deposition = {mode!r}: one of atomic, exact")
+    return mode
+
+
 # ------------------------------------------------------------------------------------------------
 # device-side driver (needs the HIP library; imported lazily so that the host-only helpers above
 # stay usable without a GPU)
@@ -296,6 +307,11 @@ class McblockDriver:
         replicated = self.decomposition == "replicated"
         if nranks > 1 and not replicated:
             self.mesh.partition(nranks, cost=cost)
+        # (exact deposition sums per owner of a cell; a replicated mesh sums its fields over the ranks in floating point)
+        deposition = deck_deposition(pin)
+        if deposition == "exact" and replicated:
+            raise ValueError("jaybenne_amd/deposition = exact: a replicated mesh sums its fields over the ranks in "
+                             "floating point")
         if replicated:
             share = self.pkg.Param("num_particles") / nranks
         else:
@@ -320,6 +336,12 @@ class McblockDriver:
         order = deck_cell_order(pin)
         if order != self.md.cell_order:
             self.md.cell_order = order
+        # (nor this one: energy_delta and the census tally as one rounding of the exact sum -- deposition = exact)
+        # (the key was read in front of the MeshData; without it the library's default stands, which JB_DEPOSITION sets)
+        if deposition is None and self.md.deposition == "exact" and replicated:
+            raise ValueError("JB_DEPOSITION=exact: a replicated mesh sums its fields over the ranks in floating point")
+        if deposition is not None and deposition != self.md.deposition:
+            self.md.deposition = deposition
         # (nor these: the boundary source -- a black wall of temperature bsource_<face>_temperature behind a domain
         # face, bsource_num_particles photons per cycle over all such faces; every temperature 0 = off)
         self.md.bsource_num_particles = pin.GetOrAddInteger("jaybenne_amd", "bsource_num_particles", 0)
