@@ -91,6 +91,17 @@ std::shared_ptr<StateDescriptor> Initialize(ParameterInput *pin, Opacity &opacit
   int device = 0;
   (void)hipGetDevice(&device);   // the device Kokkos::initialize selected for this rank
   JB_REQUIRE(jb_initialize(&p, &e, &o, &s, device, &st->ctx));
+  // (not a key of the reference: <jaybenne_amd> source_tilt = none | linear -- SourcePhotons places new photons along
+  // the gradient of T^4, jaybenne_amd.h: jb_set_source_tilt; without the key the library's default, which
+  // JB_SOURCE_TILT sets)
+  {
+    const std::string tilt = pin->GetOrAddString("jaybenne_amd", "source_tilt", "");
+    if (tilt == "none" || tilt == "linear") {
+      JB_REQUIRE(jb_set_source_tilt(st->ctx, tilt == "linear" ? JB_TILT_LINEAR : JB_TILT_NONE));
+    } else if (!tilt.empty()) {
+      PARTHENON_FAIL("jaybenne_amd/source_tilt: one of none, linear");
+    }
+  }
   pkg->AddParam<>("amd_state", st);
   pkg->AddParam<>("num_particles", (int)p.num_particles);
   pkg->AddParam<>("dt", p.dt);

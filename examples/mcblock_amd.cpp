@@ -589,6 +589,12 @@ int main(int argc, char **argv) {
       const std::string dep = pin.GetOrAddString("jaybenne_amd", "deposition", "");
       if (!dep.empty()) jb::SetDeposition(&md, jb::DepositionOf(dep));
     }
+    // (as the Python driver: source_tilt = linear -- new photons placed along the gradient of T^4; without the key
+    // the library's default, which JB_SOURCE_TILT sets)
+    {
+      const std::string tilt = pin.GetOrAddString("jaybenne_amd", "source_tilt", "");
+      if (!tilt.empty()) jb::SetSourceTilt(&md, jb::SourceTiltOf(tilt));
+    }
     // (as the Python driver: the boundary source -- a black wall of temperature bsource_<face>_temperature behind a
     // domain face, bsource_num_particles photons per cycle over all such faces; every temperature 0 = off)
     md.bsource_num_particles = pin.GetOrAddInteger("jaybenne_amd", "bsource_num_particles", 0);

@@ -830,6 +830,46 @@ jb_status jb_deposit_last(jb_context *ctx, jb_deposit_stats *out);
 int64_t jb_deposit_memory(const jb_mesh *mesh);
 int64_t jb_deposit_kernel_launches(const jb_context *ctx);
 
+/* ---- source tilt -- where in its cell a new photon starts (jaybenne_amd/csrc/jb_kernel_tilt.hpp).  The reference
+ * places every new photon uniformly in its cell (sourcing.cpp:175-177): a cell is isothermal, and in a cell that is
+ * optically thick to absorption the energy absorbed at its hot face is re-emitted, on average, at its centre --
+ * half a cell downstream every cycle.  Under JB_TILT_LINEAR the emission probability of SourcePhotons, thermal and
+ * emission, varies linearly within a cell along every active axis, following the gradient of T^4 (Fleck and
+ * Cummings' source tilt).  The boundary source, whose photons start on a face, is not tilted.  The contract:
+ *   - Slopes.  jb_source_photons_count, behind its count kernel and only in this mode, computes for every interior
+ *     cell of every owned resident block and every active axis d one slope s_d in [-1, 1]:
+ *       E = (T T) (T T), T = the temperature of (rho, sie) exactly as the count forms it;
+ *       E_c the cell's, E_m / E_p its lower / upper neighbour's along d -- read from the block's own ghost layer
+ *       where the neighbour lies in another block (the host keeps those ghosts current, as for the DDMC face
+ *       probabilities; across a level change this is what the host's ghost fill put there, at the block's own
+ *       spacing).  A neighbour beyond a domain face whose swarm boundary is not periodic counts as E_c, and that
+ *       ghost cell is not read;
+ *       s_raw = (E_p - E_m) / (4 E_c);  s = min(max(s_raw, -1), 1);  s = 0 if E_c is zero or s_raw is not finite.
+ *     Every operation is rounded on its own.  Inactive axes have s = 0.
+ *   - Sampling.  With xi the draw the photon takes for that axis (draw order and count are those of JB_TILT_NONE,
+ *     so everything drawn behind the positions keeps its bits):
+ *       a = 1 - s;  D = sqrt(a a + (4 s) xi);  u = ((4 xi - 2) + s) / (1 + D);
+ *       u = max(min(u, 1 - 2^-52), -1);  x = xc + (0.5 dx) u
+ *     -- two products, one sum and one correctly rounded square root for D (a radicand that rounding took to 0 or
+ *     below has D = 0), one correctly rounded quotient, no fused operation.  This inverts the density (1 + s u) / 2
+ *     on [-1, 1] without cancellation for small s; for s = 0 it returns 2 xi - 1 exactly and x has the bits of
+ *     xc + dx (xi - 0.5).  The position is a function of (s, xi, xc, dx) alone.
+ *   - jb_source_photons_fill / _fill_range in this mode read the slopes of the mesh's last count call; without one
+ *     in this mode they return JB_ERR_INVALID.  Ids and draws do not depend on the mode: a replicated mesh and
+ *     several ranks source the photons of one rank.  jb_radiation_step and jb_radiation_step_ranks source through
+ *     these calls and take the mode from the context.
+ *   - The slopes live in a library-owned array of 8 ndim bytes per interior cell of the resident blocks, taken at
+ *     the mesh's first count call in this mode and freed with the mesh.
+ * With JB_TILT_NONE (the default) no kernel of jb_kernel_tilt.hpp is launched and every call gives the bits it
+ * gave.  JB_SOURCE_TILT=linear in the environment makes LINEAR the default of jb_initialize, like JB_DEPOSITION. */
+enum { JB_TILT_NONE = 0, JB_TILT_LINEAR = 1 };
+jb_status jb_set_source_tilt(jb_context *ctx, int mode);
+int jb_get_source_tilt(const jb_context *ctx);
+/* The slopes of the mesh's last count call of resident block local_block, copied to out_host as [3][ncell]
+ * doubles, cells in (k, j, i) order, zeros for inactive axes (synchronises the context's stream).
+ * JB_ERR_INVALID if that call was not made under JB_TILT_LINEAR (or none was made), or for a halo copy. */
+jb_status jb_source_tilt_slopes(jb_context *ctx, const jb_mesh *mesh, int local_block, double *out_host);
+
 /* ---- transport invariants (checked library) -- the reference's PARTHENON_DEBUG_REQUIREs of the
  * tracking loop and of SampleDDMCBlockFace, evaluated on every pass (jaybenne_amd/csrc/jb_invariants.hpp).
  * `make -C jaybenne_amd/csrc checked` builds libjaybenne_amd_checked.so from the same sources with

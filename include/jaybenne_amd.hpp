@@ -693,6 +693,16 @@ inline int DepositionOf(const std::string &value) {
   if (value == "exact") return JB_DEPOSIT_EXACT;
   throw std::invalid_argument("jaybenne_amd/deposition = '" + value + "': one of atomic, exact");
 }
+// source tilt: JB_TILT_NONE (default) or JB_TILT_LINEAR -- SourcePhotons places a new photon in its cell along the
+// gradient of T^4 taken from the neighbouring cells (jaybenne_amd.h: jb_set_source_tilt); ids and draws are the same
+inline void SetSourceTilt(MeshData *md, int mode) { Check(jb_set_source_tilt(md->ctx(), mode)); }
+inline int GetSourceTilt(MeshData *md) { return jb_get_source_tilt(md->ctx()); }
+// the mode of the deck key <jaybenne_amd> source_tilt = none | linear
+inline int SourceTiltOf(const std::string &value) {
+  if (value == "none") return JB_TILT_NONE;
+  if (value == "linear") return JB_TILT_LINEAR;
+  throw std::invalid_argument("jaybenne_amd/source_tilt = '" + value + "': one of none, linear");
+}
 inline Real EstimateTimestepMesh(MeshData *md) { return jb_estimate_timestep(md->ctx()); }
 
 // jaybenne::InitializeRadiation(mbd, is_thermal) -- jaybenne.cpp:570-578

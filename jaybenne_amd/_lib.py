@@ -52,6 +52,7 @@ class Scattering(C.Structure):
 ARITH_EXACT, ARITH_LEAN = 0, 1   # enum of jb_set_arithmetic
 CELL_ORDER_ANY, CELL_ORDER_BY_ID = 0, 1   # enum of jb_set_cell_order
 DEPOSIT_ATOMIC, DEPOSIT_EXACT = 0, 1      # enum of jb_set_deposition
+TILT_NONE, TILT_LINEAR = 0, 1             # enum of jb_set_source_tilt
 JB_DEPOSIT_ABSORBED, JB_DEPOSIT_ARRIVALS = 1, 2   # what jb_deposit_accumulate sweeps for (a sum of them)
 
 FIELD_IDS = {"rho": 0, "sie": 1, "u": 2, "fleck": 3, "tally": 4, "edelta": 5}   # enum jb_field
@@ -310,6 +311,9 @@ PROTOTYPES = {
     "jb_deposit_last": (_int, [_vp, C.POINTER(DepositStats)]),
     "jb_deposit_memory": (_i64, [_vp]),
     "jb_deposit_kernel_launches": (_i64, [_vp]),
+    "jb_set_source_tilt": (_int, [_vp, _int]),
+    "jb_get_source_tilt": (_int, [_vp]),
+    "jb_source_tilt_slopes": (_int, [_vp, _vp, _int, _vp]),
     "jb_debug_math": (_int, [_vp, _int, _vp, _int, _vp]),
     "jb_debug_model_coefficients": (_int, [_vp, C.POINTER(C.c_double * 4)]),
     "jb_debug_model_eval": (_int, [_vp, _int, _vp, _int, _vp]),

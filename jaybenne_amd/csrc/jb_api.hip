@@ -28,6 +28,7 @@
 #include "jb_kernel_order.hpp"
 #include "jb_kernel_bsource.hpp"
 #include "jb_kernel_deposit.hpp"
+#include "jb_kernel_tilt.hpp"
 #include "jb_select.hpp"
 
 using namespace jb;
@@ -141,6 +142,8 @@ struct jb_context {
   long long dep_launches = 0;          // kernels of jb_kernel_deposit.hpp launched so far (jb_deposit_kernel_launches)
   jb_deposit_stats dep_last{};
   bool dep_has_last = false;
+  // source tilt (jb_set_source_tilt; JB_SOURCE_TILT=linear at jb_initialize; jb_kernel_tilt.hpp): off by default
+  int source_tilt = JB_TILT_NONE;
 };
 constexpr int kLedgerHead = 64;   // words in front of the partial sums (LW_N of them used)
 constexpr int kLedgerWords = (int)(sizeof(jb_energy_ledger) / 8);
@@ -194,6 +197,11 @@ struct jb_mesh {
   bool dep_ready = false, dep_open = false;
   size_t dep_bytes = 0;                // device memory taken for the above (jb_deposit_memory)
   jb_swarm_view dep_swarm{};           // the swarm of this mesh's last accumulate: what jb_update_fluid closes with
+  // source tilt: the slopes of the last count call ([nblocks][ndim][ncell], taken at the first count call in the
+  // mode; among `owned`, so freed with the mesh), whether that call wrote them, and a host copy of the owned flags
+  double *tilt_d = nullptr;
+  bool tilt_valid = false;
+  std::vector<uint8_t> owned_host;
 };
 // open / closed: the context knows the meshes whose accumulators are open (jb_set_deposition turns a change of mode
 // down while there is one, jb_remove_marked_particles keeps their swarm's n, jb_finalize lets go of them)
@@ -480,6 +488,7 @@ extern "C" jb_status jb_initialize(const jb_params *params, const jb_eos *eos,
   }
   if (const char *e = getenv("JB_CELL_ORDER")) ctx->cell_order = strcmp(e, "id") == 0 ? JB_CELL_ORDER_BY_ID : JB_CELL_ORDER_ANY;
   if (const char *e = getenv("JB_DEPOSITION")) ctx->deposition = strcmp(e, "exact") == 0 ? JB_DEPOSIT_EXACT : JB_DEPOSIT_ATOMIC;
+  if (const char *e = getenv("JB_SOURCE_TILT")) ctx->source_tilt = strcmp(e, "linear") == 0 ? JB_TILT_LINEAR : JB_TILT_NONE;
   if (const char *e = getenv("JB_TRANSPORT_BLOCKS_PER_CU")) ctx->blocks_per_cu_env = atoi(e);
   if (const char *e = getenv("JB_NO_DDMC_ALL")) ctx->no_ddmc_all = e[0] == '1';
   if (const char *e = getenv("JB_NO_IMC_CELL")) ctx->no_imc_cell = e[0] == '1';
@@ -716,6 +725,8 @@ extern "C" jb_status jb_mesh_create(jb_context *ctx, const jb_mesh_view *v, jb_m
   m->nranks_seen = maxrank + 1;
   m->gid_host.assign(v->gid, v->gid + v->nblocks);
   for (int b = 0; b < v->nblocks; ++b) m->nowned += (!v->owned || v->owned[b]) ? 1 : 0;
+  m->owned_host.assign((size_t)v->nblocks, 1);
+  for (int b = 0; v->owned && b < v->nblocks; ++b) m->owned_host[(size_t)b] = v->owned[b] ? 1 : 0;
   for (int g = 1; g < v->nblocks_total; ++g) m->one_owner = m->one_owner && v->owner[g] == v->owner[0];
   m->bface_host.assign(6 * (size_t)v->nblocks, 0);
   for (int b = 0; b < v->nblocks; ++b)
@@ -1026,6 +1037,23 @@ extern "C" jb_status jb_source_photons_count(jb_context *ctx, jb_mesh *mesh, int
   hipLaunchKernelGGL(k_source_count, dim3(M.nblocks), dim3(kBlock), 0, ctx->stream, M, ctx->dp,
                      source_type, dt, npc, epoch, nper_d, prefix_dev);
   JB_HIP(hipGetLastError());
+  // (source tilt: the slopes of T^4 this call's photons are placed by, from the state the count read)
+  mesh->tilt_valid = false;
+  if (ctx->source_tilt == JB_TILT_LINEAR) {
+    if (M.ng < 1) return fail(JB_ERR_INVALID, "source tilt: the blocks have no ghost layer to read the neighbours from");
+    if (!mesh->tilt_d) {
+      double *p = nullptr;
+      JB_HIP(hipMalloc(&p, sizeof(double) * (size_t)M.nblocks * (size_t)M.ndim * (size_t)M.ncell));
+      mesh->owned.push_back(p);
+      mesh->tilt_d = p;
+    }
+    const dim3 g(grid_for(ctx, (long long)M.nblocks * M.ncell));
+    if (M.ndim == 1) hipLaunchKernelGGL(k_source_tilt<1>, g, dim3(kBlock), 0, ctx->stream, M, ctx->dp, mesh->tilt_d);
+    else if (M.ndim == 2) hipLaunchKernelGGL(k_source_tilt<2>, g, dim3(kBlock), 0, ctx->stream, M, ctx->dp, mesh->tilt_d);
+    else hipLaunchKernelGGL(k_source_tilt<3>, g, dim3(kBlock), 0, ctx->stream, M, ctx->dp, mesh->tilt_d);
+    JB_HIP(hipGetLastError());
+    mesh->tilt_valid = true;
+  }
   JB_HIP(hipMemcpyAsync(nper_block_host, nper_d, sizeof(int) * M.nblocks, hipMemcpyDeviceToHost,
                         ctx->stream));
   JB_HIP(hipStreamSynchronize(ctx->stream));
@@ -1062,6 +1090,10 @@ extern "C" jb_status jb_source_photons_fill_range(jb_context *ctx, jb_mesh *mesh
   if (source_type == JB_SOURCE_EMISSION && !ctx->params.do_emission) return JB_COMPLETE;
   st = ensure_scratch(ctx, (size_t)M.nblocks * 5 + 8);
   if (st != JB_COMPLETE) return st;
+  const bool tilted = ctx->source_tilt == JB_TILT_LINEAR;
+  if (tilted && !mesh->tilt_valid)
+    return fail(JB_ERR_INVALID, "jb_source_photons_fill: source tilt is linear, but the mesh's last count call was not "
+                                "made in that mode");
   const int32_t *nper = nper_block_host;
   std::vector<long long> tab(4 * (size_t)M.nblocks);
   long long total = 0;
@@ -1086,13 +1118,20 @@ extern "C" jb_status jb_source_photons_fill_range(jb_context *ctx, jb_mesh *mesh
   // replicated-mesh run but one, so that the sum over ranks carries the emission once)
   hipLaunchKernelGGL(k_source_edelta, dim3(grid_for(ctx, (long long)M.nblocks * M.ncell)),
                      dim3(kBlock), 0, ctx->stream, M, set_energy_delta ? source_type : 0);
-  if (total > 0)
+  if (total > 0 && !tilted)
     hipLaunchKernelGGL(k_source_fill, dim3(grid_for(ctx, total)), dim3(kBlock), 0, ctx->stream, M,
                        ctx->dp, dev_swarm(swarm), source_type, t_start, dt, (const int *)prefix_dev,
                        (const long long *)tab_d, (const long long *)(tab_d + M.nblocks),
                        (const unsigned long long *)(tab_d + 2 * M.nblocks),
                        first_in_block_host ? (const long long *)(tab_d + 3 * M.nblocks) : (const long long *)nullptr,
                        total);
+  if (total > 0 && tilted)   // (source tilt: the same photons, placed by the slopes of the count call)
+    hipLaunchKernelGGL(k_source_fill_tilt, dim3(grid_for(ctx, total)), dim3(kBlock), 0, ctx->stream, M,
+                       ctx->dp, dev_swarm(swarm), source_type, t_start, dt, (const int *)prefix_dev,
+                       (const long long *)tab_d, (const long long *)(tab_d + M.nblocks),
+                       (const unsigned long long *)(tab_d + 2 * M.nblocks),
+                       first_in_block_host ? (const long long *)(tab_d + 3 * M.nblocks) : (const long long *)nullptr,
+                       total, (const double *)mesh->tilt_d);
   JB_HIP(hipGetLastError());
 #ifdef JB_INVARIANTS
   {  // (checked build) SWARM over the slots just filled
@@ -1107,6 +1146,36 @@ extern "C" jb_status jb_source_photons_fill_range(jb_context *ctx, jb_mesh *mesh
   }
 #endif
   JB_HIP(hipStreamSynchronize(ctx->stream));  // tab lives on this stack frame
+  return JB_COMPLETE;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The source tilt (jb_kernel_tilt.hpp): the slopes are written by jb_source_photons_count, read by the fill.
+extern "C" jb_status jb_set_source_tilt(jb_context *ctx, int mode) {
+  if (!ctx || (mode != JB_TILT_NONE && mode != JB_TILT_LINEAR))
+    return fail(JB_ERR_INVALID, "jb_set_source_tilt: mode = %d is neither JB_TILT_NONE nor JB_TILT_LINEAR", mode);
+  ctx->source_tilt = mode;
+  return JB_COMPLETE;
+}
+extern "C" int jb_get_source_tilt(const jb_context *ctx) {
+  return ctx && ctx->source_tilt == JB_TILT_LINEAR ? JB_TILT_LINEAR : JB_TILT_NONE;
+}
+
+extern "C" jb_status jb_source_tilt_slopes(jb_context *ctx, const jb_mesh *mesh, int local_block, double *out_host) {
+  if (!ctx || !mesh || !out_host) return fail(JB_ERR_INVALID, "jb_source_tilt_slopes: null argument");
+  const DevMesh &M = mesh->dm;
+  if (local_block < 0 || local_block >= M.nblocks)
+    return fail(JB_ERR_INVALID, "jb_source_tilt_slopes: block %d outside 0..%d", local_block, M.nblocks - 1);
+  if (!mesh->tilt_valid || !mesh->tilt_d)
+    return fail(JB_ERR_INVALID, "jb_source_tilt_slopes: the mesh's last count call was not made under JB_TILT_LINEAR");
+  if (!mesh->owned_host[(size_t)local_block])
+    return fail(JB_ERR_INVALID, "jb_source_tilt_slopes: block %d is a halo copy: its owner has the slopes", local_block);
+  JB_HIP(hipSetDevice(ctx->device));
+  const size_t n = (size_t)M.ndim * (size_t)M.ncell;
+  for (size_t q = n; q < 3 * (size_t)M.ncell; ++q) out_host[q] = 0.0;
+  JB_HIP(hipMemcpyAsync(out_host, mesh->tilt_d + (size_t)local_block * n, sizeof(double) * n, hipMemcpyDeviceToHost,
+                        ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
   return JB_COMPLETE;
 }
 

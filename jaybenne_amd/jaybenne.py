@@ -443,6 +443,28 @@ class MeshData:
             raise ValueError("deposition = 'exact': a replicated mesh sums its fields over the ranks in floating point")
         _lib.check(self.lib.jb_set_deposition(self.pkg.ctx, deposition_code(mode)))
 
+    # ---- source tilt
+    @property
+    def source_tilt(self) -> str:
+        """``"none"`` (the default) or ``"linear"``: within a cell the emission probability of ``SourcePhotons``
+        follows the gradient of T^4 taken from the neighbouring cells instead of being uniform
+        (include/jaybenne_amd.h: ``jb_set_source_tilt``).  Ids and draws do not depend on it."""
+        return SOURCE_TILTS[self.lib.jb_get_source_tilt(self.pkg.ctx)]
+
+    @source_tilt.setter
+    def source_tilt(self, mode: str) -> None:
+        _lib.check(self.lib.jb_set_source_tilt(self.pkg.ctx, source_tilt_code(mode)))
+
+    def source_tilt_slopes(self) -> np.ndarray:
+        """The slopes of the last ``SourcePhotons`` count under ``linear``, ``[owned blocks, 3, nx3, nx2, nx1]``
+        (``jb_source_tilt_slopes``; zeros on inactive axes)."""
+        m = self.mesh
+        out = np.zeros((self.nowned, 3, m.ncell), dtype=np.float64)
+        self._sync_stream()
+        for b in range(self.nowned):
+            _lib.check(self.lib.jb_source_tilt_slopes(self.pkg.ctx, self.handle, b, out[b].ctypes.data))
+        return out.reshape((self.nowned, 3) + tuple(int(n) for n in m.nx[::-1]))
+
     def deposit_close(self) -> dict:
         """``jb_deposit_close`` on this rank's swarm, then the counts of that close (``jb_deposit_last``)."""
         self._sync_stream()
@@ -811,6 +833,20 @@ def DefragParticles(md: MeshData) -> TaskStatus:
 
 CELL_ORDERS = ("any", "id")
 DEPOSITIONS = ("atomic", "exact")
+SOURCE_TILTS = ("none", "linear")
+
+
+def source_tilt_code(mode: str, key: str = "source_tilt") -> int:
+    """``JB_TILT_NONE`` / ``_LINEAR`` of ``none`` / ``linear`` (the values of the deck key
+    ``<jaybenne_amd> source_tilt``); anything else is an error that names ``key``."""
+    if mode not in SOURCE_TILTS:
+        raise ValueError(f"{key} = {mode!r}: one of none, linear")
+    return SOURCE_TILTS.index(mode)
+
+
+def SetSourceTilt(md: "MeshData", mode: str) -> None:
+    """``md.source_tilt = mode``: ``"none"`` or ``"linear"`` (include/jaybenne_amd.h: ``jb_set_source_tilt``)."""
+    md.source_tilt = mode
 
 
 def deposition_code(mode: str, key: str = "deposition") -> int:

@@ -267,6 +267,17 @@ def deck_deposition(pin: ParameterInput) -> str:
     return mode
 
 
+def deck_source_tilt(pin: ParameterInput) -> str:
+    """``<jaybenne_amd> source_tilt = none | linear``; without the key ``None`` (the library's default, which
+    JB_SOURCE_TILT sets); anything else raises with the key named."""
+    mode = pin.GetOrAddString("jaybenne_amd", "source_tilt", "").strip()
+    if mode == "":
+        return None
+    if mode not in ("none", "linear"):
+        raise ValueError(f"jaybenne_amd/source_tilt = {mode!r}: one of none, linear")
+    return mode
+
+
 # ------------------------------------------------------------------------------------------------
 # device-side driver (needs the HIP library; imported lazily so that the host-only helpers above
 # stay usable without a GPU)
@@ -342,6 +353,11 @@ class McblockDriver:
             raise ValueError("JB_DEPOSITION=exact: a replicated mesh sums its fields over the ranks in floating point")
         if deposition is not None and deposition != self.md.deposition:
             self.md.deposition = deposition
+        # (nor this one: new photons placed in their cell along the gradient of T^4 -- source_tilt = linear; set in
+        # front of InitializeRadiation, whose thermal source it covers too)
+        tilt = deck_source_tilt(pin)
+        if tilt is not None and tilt != self.md.source_tilt:
+            self.md.source_tilt = tilt
         # (nor these: the boundary source -- a black wall of temperature bsource_<face>_temperature behind a domain
         # face, bsource_num_particles photons per cycle over all such faces; every temperature 0 = off)
         self.md.bsource_num_particles = pin.GetOrAddInteger("jaybenne_amd", "bsource_num_particles", 0)
