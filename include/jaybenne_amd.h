@@ -956,7 +956,9 @@ jb_status jb_debug_draw_stream(jb_context *ctx, uint64_t state, int n, double *o
 /* which: 0 log, 1 sin, 2 cos, 3 acos, 4 sqrt, 5 reciprocal, 6 lean sqrt, 7 lean x[i] / x[i+1],
  * 8 lean x[i] / c, 9 sin(2 pi x), 10 cos(2 pi x), 11 1 - exp(-x), 12 x[i] / x[i+1] as the lean
  * arithmetic forms it (numerator times once-refined reciprocal), 13 lean log, 14 lean sqrt, 15 lean log
- * on its 1024-row table (the cell-local IMC kernel's) */
+ * on its 1024-row table (the cell-local IMC kernel's), 16 / 17 sin / cos(2 pi x) with the grid point rounded by
+ * adding the magic constant 2^44 + 2^43 to x (the scatter's form for generator uniforms; equal to 9 / 10 unless 256 x is
+ * an integer plus one half) */
 jb_status jb_debug_math(jb_context *ctx, int which, const double *x_host, int n, double *out_host);
 /* the opacity / scattering models as the kernels evaluate them: out[0..3] = EPBremss A, B, E
  * (sigma_a = A rho^2 T^-1/2 (1 - e^(-B nu / T)) nu^-3, j = E rho^2 T^1/2, code units) and the
@@ -978,7 +980,9 @@ jb_status jb_debug_step_call(jb_context *ctx, int which, jb_debug_step *st, cons
                              int ntape, int *ndraws);
 /* which: 0 scatter(vv), 1 sample_face_iso_dir(vv), 2 sample_Planck_energy(sb=a0, temp=a1),
  * 3 SampleFace2D(i_l=i0, dx=a0, P_l=a1, P_u=a2; i=i1, x=a3),
- * 4 SampleFace3D(i1_l=i0, i2_l=i1, dx1=a0, dx2=a1, P=a2..a5; i=(i2,i3), x=(a6,a7)) */
+ * 4 SampleFace3D(i1_l=i0, i2_l=i1, dx1=a0, dx2=a1, P=a2..a5; i=(i2,i3), x=(a6,a7)),
+ * 5 scatter_dir (the unit direction the lean tracking kernels scatter into; on a tape the azimuth keeps the
+ *   conversion form of jb_debug_math 9 / 10) */
 jb_status jb_debug_sample_call(jb_context *ctx, int which, const double *a, const int32_t *i,
                                const double *tape, int ntape, double out[4], int32_t iout[2],
                                int *ndraws);

@@ -3529,6 +3529,8 @@ __global__ void k_dbg_math(int which, const double *x, int n, double *out) {
     case 12: out[i] = x[i] * m_rcp_once(x[(i + 1) % n]); break;   // lean quotient
     case 13: out[i] = m_log_lean(x[i]); break;
     case 15: out[i] = m_log_lean<false, true>(x[i]); break;
+    case 16: m_sincos2pi<false, true>(x[i], s, c); out[i] = s; break;   // grid point by the magic constant
+    case 17: m_sincos2pi<false, true>(x[i], s, c); out[i] = c; break;
     default: out[i] = m_sqrt_lean(x[i]); break;
     }
   }
@@ -3578,6 +3580,8 @@ __global__ void k_dbg_sample(int which, const double *a, const int *iv, const do
     sample_face_iso_dir(a[0], rng, out[0], out[1], out[2]);
   } else if (which == 2) {
     out[0] = sample_planck_energy(rng, a[0], a[1]);
+  } else if (which == 5) {   // the tracking kernels' scatter in direction space, on the tape generator
+    scatter_dir(rng, out[0], out[1], out[2]);
   } else if (which == 3) {
     int i = iv[1];
     double x = a[3];

@@ -73,7 +73,9 @@ namespace jb {
 #endif
 // The step's nudge and re-indexing under one exec mask per axis (jb_physics.hpp: nudge_reindex_masked), 6 instead
 // of 8 vector instructions per axis: every instantiation (C2 52.96 -> 50.59, C4 42.36 -> 41.00 ms per step; registers
-// and scratch unchanged in all of them).  0 = the select form with its inline-asm v_bfi_b32 / v_cndmask_b32.
+// and scratch unchanged in all of them; 5 per axis since the high word of p is one v_bitop3_b32: with the carried run
+// mask below and the scatter's azimuth by addition C2 50.60 -> 48.77, C4 41.01 -> 39.90 ms per step).
+// 0 = the select form with its inline-asm v_bfi_b32 / v_cndmask_b32.
 #ifndef JB_IMC_MASKED_NUDGE
 #define JB_IMC_MASKED_NUDGE 1
 #endif
@@ -335,7 +337,10 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
         }
       }
     }
-    const int running = __popcll(__ballot(ls == IS_RUN));
+    // the running lanes as a wave mask: a pass of the event loop takes it from here and leaves the next one's behind
+    // (nothing writes ls between the end of a pass and the top of the next: one comparison per pass, not two)
+    unsigned long long run_m = __builtin_amdgcn_ballot_w64(ls == IS_RUN);
+    const int running = __popcll(run_m);
     if (running == 0) {
       if (__ballot(ls != IS_IDLE) != 0ull || qcur.more) continue;
       break;
@@ -346,6 +351,7 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
     int thresh = 1;
     int nrun = running;
     while (nrun >= thresh) {
+#if JB_IMC_PARENT_RUNMASK
       const bool run = ls == IS_RUN;
       // ---- a photon in a ghost cell: it has left its block (transport.cpp:149-155)
       const bool cross = run && lam_s < 0.0;
@@ -354,6 +360,14 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
       // a vector register)
       const unsigned long long cross_m =
           __builtin_amdgcn_ballot_w64(ls == IS_RUN) & __builtin_amdgcn_ballot_w64(lam_s < 0.0);
+#else
+      // ---- a photon in a ghost cell: it has left its block (transport.cpp:149-155)
+      // (the carried mask and the ballot of the one comparison, combined as scalars; a lane's predicate is its bit)
+      const unsigned long long cross_m = run_m & __builtin_amdgcn_ballot_w64(lam_s < 0.0);
+      const bool cross = __builtin_amdgcn_inverse_ballot_w64(cross_m);
+      // (a crossing lane sits this pass out: the new cell's datum is on its way)
+      const bool stepping = __builtin_amdgcn_inverse_ballot_w64(run_m & ~cross_m);
+#endif
       c_evp += (1ull << 40) + (unsigned long long)(nrun - __popcll(cross_m));
       if (cross_m != 0ull) {
         if (cross) {
@@ -446,7 +460,8 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
           if (census && !off) ls = IS_DONE;
         }
       }
-      nrun = __popcll(__ballot(ls == IS_RUN));
+      run_m = __builtin_amdgcn_ballot_w64(ls == IS_RUN);
+      nrun = __popcll(run_m);
       waste += running - nrun;
       if (waste >= kServiceBudget) thresh = 65;
     }

@@ -29,6 +29,28 @@
 
 namespace jb {
 
+// Three trims of k_imc_cell's pass and their earlier forms, each behind a macro of its own (1 = the earlier form):
+//   JB_IMC_PARENT_NUDGE    the nudge's high word by v_bfi_b32 + v_xor_b32 instead of one v_bitop3_b32 (jb_physics.hpp)
+//   JB_IMC_PARENT_RUNMASK  `ls == IS_RUN` compared at the top of a pass again instead of the mask carried over from
+//                          the end of the pass before (jb_kernel_imc.hpp)
+//   JB_IMC_PARENT_AZIMUTH  the scatter's azimuth grid point by two conversions instead of the magic constant
+//                          (m_sincos2pi below)
+// -DJB_IMC_PARENT_FORMS sets all three (`make parent_forms`: the library tests/test_gpu_imc_trims.py compares the
+// release with, bit for bit, and the partner of an A/B on one tree).
+#ifdef JB_IMC_PARENT_FORMS
+#define JB_IMC_PARENT_NUDGE 1
+#define JB_IMC_PARENT_RUNMASK 1
+#define JB_IMC_PARENT_AZIMUTH 1
+#endif
+#ifndef JB_IMC_PARENT_NUDGE
+#define JB_IMC_PARENT_NUDGE 0
+#endif
+#ifndef JB_IMC_PARENT_RUNMASK
+#define JB_IMC_PARENT_RUNMASK 0
+#endif
+#ifndef JB_IMC_PARENT_AZIMUTH
+#define JB_IMC_PARENT_AZIMUTH 0
+#endif
 
 // fma through the 3-address VOP3 form.  Left to itself the compiler turns a Horner step
 // p = fma(r, p, C) with a loop-invariant constant C into "v_mov_b64 acc, C; v_fmac_f64 acc, r, p"
@@ -279,11 +301,28 @@ __device__ __forceinline__ void m_sincos(double x, double &sn, double &cs) {  //
 // reduction costs one multiplication by 2 pi of a remainder |u - i/256| <= 1/512 instead of an
 // extended-precision subtraction, and |r| <= pi/256 needs only r - r^3/6 + r^5/120 and
 // -r^2/2 + r^4/24 - r^6/720 (next terms < 1e-17).  Absolute error <= 1.7e-16.
+// MAGIC: the grid point without the two conversions.  w = u + (2^44 + 2^43) is u rounded to the nearest multiple of
+// 1/256 (ties to even) on top of the constant, whose unit in the last place is 2^-8: i is the low word of w as it
+// stands, i / 256 = w - (2^44 + 2^43) and the remainder u - i / 256 are exact -- three additions for a multiply-add,
+// two conversions and a multiply-add.  (Scaled by 256 first, fma(u, 256, 2^52 + 2^51), the sum has two constants that
+// are no inline operands and the compiler spends two v_mov_b32 on one of them per pass.)  Equal to
+// floor(256 u + 1/2) unless 256 u is exactly n + 1/2 -- which a uniform of the form (k + 1/2) 2^-52 never is (256 u
+// is an odd multiple of 2^-45) but an arbitrary double can be (1/512: grid point 0 by ties-to-even, 1 by floor), so
+// only a caller whose generator guarantees that form asks for it (Rng::kHalfOddUniforms, jb_rng.hpp: scatter_dir).
 constexpr double kTwoPiM = 6.283185307179586476925286766559;
-template <bool SC = false>
+constexpr double kRoundMagic = 26388279066624.0;  // 2^44 + 2^43
+template <bool SC = false, bool MAGIC = false>
 __device__ __forceinline__ void m_sincos2pi(double u, double &sn, double &cs) {
-  const int i = (int)fma(u, 256.0, 0.5);
-  const double r = fma((double)i, -0.00390625, u) * kTwoPiM;
+  int i;
+  double r;
+  if constexpr (MAGIC) {
+    const double w = u + kRoundMagic;
+    i = __double2loint(w);
+    r = (u - (w - kRoundMagic)) * kTwoPiM;
+  } else {
+    i = (int)fma(u, 256.0, 0.5);
+    r = fma((double)i, -0.00390625, u) * kTwoPiM;
+  }
   const double si = lds_sc2_tab[i][0], ci = lds_sc2_tab[i][1];
   const double r2 = r * r;
   const double sr = m_fma(r * r2, m_fma_k<SC>(r2, 1.0 / 120.0, -1.0 / 6.0), r);

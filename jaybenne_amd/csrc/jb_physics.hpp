@@ -426,9 +426,11 @@ __device__ __forceinline__ double nudged(double p, double m, bool hit) {
 // alone run
 //   v_med3_i32     side = clamp(high word of p, -1, 1)     (+-1 by the sign of p: the word is never 0 where |p| > m)
 //   v_mad_i32_i24  offset += side * stride                 (the stride a scalar operand)
-//   v_bfi_b32 / v_xor_b32 / v_mov_b32                      p = -copysign(m, p), word by word
-// -- 6 vector instructions per axis instead of the select form's 8 (comparison, three for the side, multiply-add,
-// v_bfi_b32 and two selects), three of them plain 32-bit operations.  The bits are the select form's; a lane
+//   v_bitop3_b32 / v_mov_b32                               p = -copysign(m, p), word by word (the high word as one
+//                                                          three-input boolean function; -DJB_IMC_PARENT_NUDGE=1:
+//                                                          v_bfi_b32 + v_xor_b32)
+// -- 5 vector instructions per axis instead of the select form's 8 (comparison, three for the side, multiply-add,
+// v_bfi_b32 and two selects), four of them plain 32-bit operations.  The bits are the select form's; a lane
 // whose comparison is false (NaN included) is not written.  One statement for all axes: exec is saved and
 // restored inside it -- the compiler never sees it changed -- and every mask is ANDed with the saved value, so a
 // lane that is not stepping is never written: 4 scalar instructions in 3-D.
@@ -440,10 +442,17 @@ constexpr bool kMaskedNudge = false;
 constexpr bool kMaskedNudge = true;
 #endif
 typedef unsigned long long lane_mask;
+#if JB_IMC_PARENT_NUDGE
+#define JB_NUDGE_HIGH(a) \
+  "v_bfi_b32 %[h" a "], %[k], %[mh" a "], %[h" a "]\n\tv_xor_b32_e32 %[h" a "], 0x80000000, %[h" a "]\n\t"
+#else
+// (k ? mh : ~h bit by bit, k = 0x7fffffff: the magnitude of m under the inverted sign of p.  Truth table over
+// a = 0xf0 (k), b = 0xcc (mh), c = 0xaa (h): (a & b) | (~a & ~c) = 0xc0 | 0x05)
+#define JB_NUDGE_HIGH(a) "v_bitop3_b32 %[h" a "], %[k], %[mh" a "], %[h" a "] bitop3:0xc5\n\t"
+#endif
 #define JB_NUDGE_AXIS(a)                                                                      \
   "v_med3_i32 %[t], %[h" a "], -1, 1\n\tv_mad_i32_i24 %[q], %[t], %[s" a "], %[q]\n\t"        \
-  "v_bfi_b32 %[h" a "], %[k], %[mh" a "], %[h" a "]\n\tv_xor_b32_e32 %[h" a "], 0x80000000, %[h" a "]\n\t" \
-  "v_mov_b32_e32 %[l" a "], %[ml" a "]\n\t"
+  JB_NUDGE_HIGH(a) "v_mov_b32_e32 %[l" a "], %[ml" a "]\n\t"
 template <int NDIM>
 __device__ __forceinline__ void nudge_reindex_masked(double &px, double &py, double &pz, unsigned &qoff, double mx,
                                                      double my, double mz, int sy, int sz, lane_mask hx,
@@ -485,6 +494,7 @@ __device__ __forceinline__ void nudge_reindex_masked(double &px, double &py, dou
   px = __hiloint2double(hix, lox);
 }
 #undef JB_NUDGE_AXIS
+#undef JB_NUDGE_HIGH
 struct NoGather {
   __device__ __forceinline__ void operator()() const {}
 };
@@ -637,7 +647,8 @@ __device__ __forceinline__ unsigned cross_level(int code, unsigned dst, int sy, 
   return dst;
 }
 
-// scattering.hpp:21-29 in direction space: the new unit direction (2 draws)
+// scattering.hpp:21-29 in direction space: the new unit direction (2 draws).  The azimuth's grid point by the magic
+// constant where the generator's uniforms cannot tie (Rng::kHalfOddUniforms): the same bits, a conversion pair less.
 template <bool SC = false, class Rng>
 __device__ __forceinline__ void scatter_dir(Rng &rng, double &ox, double &oy, double &oz) {
   double xi1, xi2;
@@ -645,7 +656,7 @@ __device__ __forceinline__ void scatter_dir(Rng &rng, double &ox, double &oy, do
   const double mu = fma(2.0, xi1, -1.0);
   const double st = m_sqrt_lean(1.0 - mu * mu);
   double sn, cs;
-  m_sincos2pi<SC>(xi2, sn, cs);
+  m_sincos2pi<SC, Rng::kHalfOddUniforms && !JB_IMC_PARENT_AZIMUTH>(xi2, sn, cs);
   ox = st * cs;
   oy = st * sn;
   oz = mu;

@@ -93,6 +93,9 @@ __device__ __forceinline__ double u52_to_double(uint64_t k52) {
 }
 
 struct LcgRng {
+  // every uniform is (k + 1/2) 2^-52: 256 u is an odd multiple of 2^-45, never an integer plus one half, so rounding
+  // it to the nearest integer has no tie to break (m_sincos2pi<.., MAGIC>, jb_math.hpp)
+  static constexpr bool kHalfOddUniforms = true;
   uint64_t s;
   __device__ __forceinline__ explicit LcgRng(uint64_t state) : s(state) {}
   __device__ __forceinline__ double drand() {
@@ -119,6 +122,7 @@ struct LcgRng {
 
 // Replays a caller-supplied list of uniforms (debug entry points / golden-vector tests only).
 struct TapeRng {
+  static constexpr bool kHalfOddUniforms = false;  // (a tape holds any double: at 1/512, 256 u = 1/2 is a tie the two forms break differently)
   const double *tape;
   int ntape;
   uint32_t ctr;
