@@ -2,7 +2,7 @@
 // what the reference's src/mcblock does around the jaybenne package, on one GPU, with no Python
 // and no PyTorch in the process.
 //
-//   mcblock_amd -i <deck> [block/key=value ...] [--tolerance X] [--dump file] [--ledger file]
+//   mcblock_amd -i <deck> [block/key=value ...] [--tolerance X] [--dump file] [--ledger file] [--moments file]
 //
 // Input deck syntax and the trailing overrides are Parthenon's (reference inputs/*.in; the
 // regression harness tst/regression_test.py:85-145 rewrites decks the same way).  It sets up the
@@ -187,7 +187,7 @@ static uint64_t Morton(const int l[3], int bits) {
 
 int main(int argc, char **argv) {
   try {
-    std::string deck, dump, ledger_path;
+    std::string deck, dump, ledger_path, moments_path;
     double tolerance = -1.0;
     std::vector<std::string> overrides;
     for (int a = 1; a < argc; ++a) {
@@ -196,10 +196,11 @@ int main(int argc, char **argv) {
       else if (s == "--tolerance" && a + 1 < argc) tolerance = std::stod(argv[++a]);
       else if (s == "--dump" && a + 1 < argc) dump = argv[++a];
       else if (s == "--ledger" && a + 1 < argc) ledger_path = argv[++a];
+      else if (s == "--moments" && a + 1 < argc) moments_path = argv[++a];
       else overrides.push_back(s);
     }
     if (deck.empty()) {
-      std::fprintf(stderr, "usage: mcblock_amd -i deck [block/key=value ...] [--tolerance X] [--dump file] [--ledger file]\n");
+      std::fprintf(stderr, "usage: mcblock_amd -i deck [block/key=value ...] [--tolerance X] [--dump file] [--ledger file] [--moments file]\n");
       return 2;
     }
     ParameterInput pin;
@@ -611,6 +612,12 @@ int main(int argc, char **argv) {
     if (!ledger_path.empty() || pin.GetOrAddBoolean("jaybenne_amd", "ledger", false)) jb::EnableLedger(&md, true);
     if (!ledger_path.empty() && !(ledger_file = std::fopen(ledger_path.c_str(), "w")))
       throw std::runtime_error("cannot write " + ledger_path);
+    // --moments FILE (or <jaybenne_amd> moments = true: moments.jsonl): after every cycle one JSON line with the
+    // report of EvaluateRadiationMoments and the domain integrals of its fields; off: none of its kernels runs
+    if (moments_path.empty() && pin.GetOrAddBoolean("jaybenne_amd", "moments", false)) moments_path = "moments.jsonl";
+    std::FILE *moments_file = nullptr;
+    if (!moments_path.empty() && !(moments_file = std::fopen(moments_path.c_str(), "w")))
+      throw std::runtime_error("cannot write " + moments_path);
     std::printf("problem %s: %d-D, %d meshblocks, %d level(s), %lld photons\n", problem_id.c_str(), ndim,
                 nb, max_level + 1, (long long)md.swarm.n);
 
@@ -648,9 +655,17 @@ int main(int argc, char **argv) {
       if (!md.comb_history.empty() && md.comb_history.back().cycle == (int64_t)md.cycle)
         std::printf(" combed=%lld new_ids=%lld", (long long)md.comb_history.back().cells_combed,
                     (long long)md.comb_history.back().n_new_ids);
+      if (moments_file) {
+        jb_moments_report rep{};
+        const std::vector<double> mom = jb::EvaluateRadiationMoments(&md, &rep);
+        const jb::MomentsIntegrals I = jb::IntegrateMoments(mom, nb, (int64_t)ncell, dx.data(), opacity.c);
+        std::fprintf(moments_file, "%s\n", jb::MomentsJson(md.cycle, time, rep, I).c_str());
+        std::printf(" eddington=[%.4f, %.4f, %.4f]", I.eddington[0], I.eddington[1], I.eddington[2]);
+      }
       std::printf("\n");
     }
     if (ledger_file) std::fclose(ledger_file);
+    if (moments_file) std::fclose(moments_file);
     if (jb::LedgerEnabled(&md)) {   // totals by face
       static const char *const kFaces[6] = {"ix1", "ox1", "ix2", "ox2", "ix3", "ox3"};
       std::printf("leakage by face:");

@@ -535,6 +535,62 @@ jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swa
 jb_status jb_comb_census_apply(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, uint64_t id_base,
                                jb_comb_report *out);
 
+/* ---- radiation moments: per-cell count, energy density, flux and second-moment tensor of the census
+ * (jaybenne_amd/csrc/jb_kernel_moments.hpp).  The reference has none: energy_tally is the zeroth angular moment
+ * alone, and its tests copy the swarm to the host for anything else.  Called between two cycles.
+ * For every interior cell of every OWNED resident block, JB_MOMENTS = 12 doubles over the ACTIVE photons whose
+ * sort key is that cell -- the key jb_defrag_particles orders by: the cell of the photon's POSITION clamped to the
+ * block's array (not ip, jp, kp).  With v = c Omega the photon's velocity, p_d = w v_d and dv = (dx0 dx1) dx2 of
+ * the block, as the energy tally forms it:
+ *     JB_MOM_N              the number of photons, as a double
+ *     JB_MOM_E              (sum of w) / dv                 the energy density (energy_tally, summed otherwise)
+ *     JB_MOM_W2             sum of w w                      N_eff = (E dv)^2 / W2 equal-weight photons stand behind E
+ *     JB_MOM_FX, FY, FZ     (sum of p_d) / dv               the energy flux
+ *     JB_MOM_QXX .. QZZ     (sum of p_i v_j) / dv, i <= j   Q / c^2 is the pressure tensor, Q_ij / (c^2 E) Eddington's
+ * Every product is rounded on its own, the division is one rounding of the sum, and all three velocity components
+ * take part whatever ndim is.  Cells of halo copies and empty cells get twelve zeros: every word of out_dev is
+ * written.  Not counted (report->n_skipped): slots that are not ACTIVE, ACTIVE slots whose blk is outside
+ * [0, nblocks), photons of halo copies, and photons whose clamped position lies in a ghost cell.
+ * out_dev: a caller-owned device array [JB_MOMENTS][nblocks][ncell] (jb_moments_words doubles), interior cells in
+ * (k, j, i) order, blocks in the mesh's resident order.
+ * Order of summation -- what makes the result a function of the cell's photons in their slot order and of nothing
+ * else (not of the cell's offset in the swarm, the launch geometry or the run): the cell's photons are a run of L
+ * consecutive slots a_0 .. a_(L-1) of the sorted swarm.  The run is cut into chunks of 4096 slots counted from
+ * its head; in a chunk "lane" l = 0 .. 63 starts from +0.0 and adds the elements l, l + 64, l + 128, .. in rising
+ * order; the 64 lane sums are joined by  for d in 32, 16, 8, 4, 2, 1: s[l] = s[l] + s[l + d] for l < d;  the run's
+ * sum is the first chunk's sum with the further chunks' sums added in chunk order.  No floating-point atomics.
+ * The call asks "in (block, cell) order already?" as jb_comb_census_plan does and sorts with jb_defrag_particles
+ * if not (report->sorted; for jb_defrag_policy that counts as a sort, exactly as a comb plan that sorted does).
+ * JB_CELL_ORDER_ANY: the order within a cell is then whatever the sort left, and a swarm already in key order is
+ * not moved -- the same sorted swarm gives the same bits.  JB_CELL_ORDER_BY_ID: the question is "in canonical
+ * order?", the sort the canonical one, and the result a function of the photons alone, whatever slots they came in
+ * and however the blocks are dealt to ranks.
+ * Stream synchronisations: ONE in either mode (the read-back of the order test: 4 bytes, or the 16 of the
+ * canonical sort's test), none for n = 0; ONE more when report is not NULL.  Otherwise asynchronous on the
+ * context's stream.  Scratch: what the sort takes, plus 176 bytes per 4096 photons; a comb plan not yet applied
+ * is discarded.  Limits: those of jb_defrag_particles (2^32 - 1 photons, 2^32 - 2 cells).
+ * Left as they were: energy_tally, energy_delta, open deposit accumulators, and everything a photon carries -- the
+ * slots aside, which the sort permutes.
+ * Limitation: in DDMC cells the census direction is the resampled isotropic one (reference
+ * transport_utils.hpp:265-276), so there Q is the isotropic tensor and F carries no diffusive flux.
+ * JB_ERR_INVALID: a null ctx, mesh, swarm or out_dev, or the sort's limits; JB_ERR_HIP with the swarm as it was
+ * when the scratch cannot be allocated.  n = 0 is valid and writes zeros.
+ * Opens the trace range "Jaybenne::EvaluateRadiationMoments". */
+enum { JB_MOM_N = 0, JB_MOM_E, JB_MOM_W2, JB_MOM_FX, JB_MOM_FY, JB_MOM_FZ,
+       JB_MOM_QXX, JB_MOM_QXY, JB_MOM_QXZ, JB_MOM_QYY, JB_MOM_QYZ, JB_MOM_QZZ, JB_MOMENTS };
+typedef struct jb_moments_report {
+  int64_t n_counted, n_skipped;      /* slots of [0, n) summed / not summed */
+  int64_t cells_nonempty, longest_run;
+  int32_t sorted, pad;               /* 1: the call had to sort */
+} jb_moments_report;
+int64_t jb_moments_words(const jb_mesh *mesh);      /* JB_MOMENTS * nblocks * ncell */
+jb_status jb_evaluate_radiation_moments(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
+                                        double *out_dev, jb_moments_report *report /* or NULL */);
+/* The same into a HOST array of jb_moments_words doubles, for a host that allocates no device memory of its own:
+ * through a device array the context keeps (jb_release_scratch returns it); synchronises the stream at the end. */
+jb_status jb_evaluate_radiation_moments_host(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
+                                             double *out_host, jb_moments_report *report /* or NULL */);
+
 /* MeshSend / MeshReceive (jaybenne.cpp:36-61) for the inter-rank part: OUTGOING particles are
  * among [first,last) are copied into fixed-size records (JB_RECORD_WORDS x 8 bytes), ordered by
  * destination rank, and their slots are re-marked JB_ST_ABSORBED-like holes (status

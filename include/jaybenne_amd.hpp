@@ -763,6 +763,63 @@ inline void CombAfterStep(MeshData *md, int64_t events) {
   DefragAfterStep(md, events);
 }
 
+// ---- radiation moments (jaybenne_amd.h: jb_evaluate_radiation_moments): only when a host asks -------------
+// Per-cell count, energy density, sum of squared weights, flux and second-moment tensor of the census as a host
+// array [JB_MOMENTS][nblocks][ncell] (interior cells in (k, j, i) order; zeros in halo copies).  Sorts the swarm
+// by (block, cell) when it is not in that order.
+inline std::vector<double> EvaluateRadiationMoments(MeshData *md, jb_moments_report *report = nullptr) {
+  std::vector<double> out((size_t)jb_moments_words(md->mesh()));
+  Check(jb_evaluate_radiation_moments_host(md->ctx(), md->mesh(), &md->swarm, out.data(), report));
+  return out;
+}
+// The domain integrals a command-line host prints per cycle: n, e = sum E dv, w2, f = sum F dv, q = sum Q dv, each
+// summed sequentially in (component, block, cell) order -- every host forms them this way, so that two hosts print
+// the same digits for the same run -- and eddington[d] = q_dd / (c^2 e).  blk_dx: [nblocks][3], as jb_mesh_view's.
+struct MomentsIntegrals {
+  double n = 0.0, e = 0.0, w2 = 0.0, f[3] = {0.0, 0.0, 0.0}, q[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double eddington[3] = {0.0, 0.0, 0.0};
+};
+inline MomentsIntegrals IntegrateMoments(const std::vector<double> &m, int nblocks, int64_t ncell, const double *blk_dx,
+                                         double c) {
+  double s[JB_MOMENTS];
+  for (int comp = 0; comp < JB_MOMENTS; ++comp) {
+    const bool per_volume = comp != JB_MOM_N && comp != JB_MOM_W2;
+    double acc = 0.0;
+    for (int b = 0; b < nblocks; ++b) {
+      const double dv = (blk_dx[3 * b] * blk_dx[3 * b + 1]) * blk_dx[3 * b + 2];
+      const double *v = m.data() + ((size_t)comp * (size_t)nblocks + (size_t)b) * (size_t)ncell;
+      for (int64_t q = 0; q < ncell; ++q) {
+        const double t = per_volume ? v[q] * dv : v[q];   // (its own statement: rounded before it is added)
+        acc += t;
+      }
+    }
+    s[comp] = acc;
+  }
+  MomentsIntegrals I;
+  I.n = s[JB_MOM_N];
+  I.e = s[JB_MOM_E];
+  I.w2 = s[JB_MOM_W2];
+  for (int d = 0; d < 3; ++d) I.f[d] = s[JB_MOM_FX + d];
+  for (int d = 0; d < 6; ++d) I.q[d] = s[JB_MOM_QXX + d];
+  const double c2e = (c * c) * I.e;
+  const int diag[3] = {0, 3, 5};
+  for (int d = 0; d < 3; ++d) I.eddington[d] = c2e > 0.0 ? I.q[diag[d]] / c2e : 0.0;
+  return I;
+}
+// one cycle's line of `--moments FILE` (the keys and digits of `python -m jaybenne_amd --moments`)
+inline std::string MomentsJson(uint64_t cycle, double time, const jb_moments_report &r, const MomentsIntegrals &I) {
+  char buf[2048];
+  const int n = std::snprintf(
+      buf, sizeof buf,
+      "{\"cycle\": %lld, \"time\": %.17g, \"n_counted\": %lld, \"n_skipped\": %lld, \"cells_nonempty\": %lld, "
+      "\"longest_run\": %lld, \"sorted\": %d, \"n\": %.17g, \"e\": %.17g, \"w2\": %.17g, \"f\": [%.17g, %.17g, %.17g], "
+      "\"q\": [%.17g, %.17g, %.17g, %.17g, %.17g, %.17g], \"eddington\": [%.17g, %.17g, %.17g]}",
+      (long long)cycle, time, (long long)r.n_counted, (long long)r.n_skipped, (long long)r.cells_nonempty,
+      (long long)r.longest_run, (int)r.sorted, I.n, I.e, I.w2, I.f[0], I.f[1], I.f[2], I.q[0], I.q[1], I.q[2], I.q[3],
+      I.q[4], I.q[5], I.eddington[0], I.eddington[1], I.eddington[2]);
+  return std::string(buf, n > 0 ? (size_t)n : 0);
+}
+
 // ---- energy ledger (jaybenne_amd.h: jb_ledger_*): off by default ----------------------------------
 inline bool LedgerEnabled(MeshData *md) { return jb_ledger_enabled(md->ctx()) == 1; }
 inline void EnableLedger(MeshData *md, bool on = true) {

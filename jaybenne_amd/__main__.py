@@ -33,6 +33,36 @@ def ledger_json(led: dict) -> str:
     return json.dumps(out)
 
 
+def moments_integrals(fields: np.ndarray, blk_dx: np.ndarray, c: float) -> dict:
+    """The domain integrals of the twelve moment fields ``[12, nblocks, ...]`` (``--moments FILE``): n, e = sum E dv,
+    w2, f = sum F dv, q = sum Q dv, each summed sequentially in (component, block, cell) order -- as
+    include/jaybenne_amd.hpp: IntegrateMoments, so that both hosts print the same digits -- and
+    eddington[d] = q_dd / (c^2 e)."""
+    nb = fields.shape[1]
+    dv = (blk_dx[:nb, 0] * blk_dx[:nb, 1]) * blk_dx[:nb, 2]
+    s = []
+    for comp in range(fields.shape[0]):
+        v = fields[comp].reshape(nb, -1)
+        if comp not in (0, 2):
+            v = v * dv[:, None]
+        s.append(float(np.add.accumulate(v.reshape(-1))[-1]) if v.size else 0.0)     # (accumulate: one by one, in order)
+    c2e = (c * c) * s[1]
+    return dict(n=s[0], e=s[1], w2=s[2], f=s[3:6], q=s[6:12],
+                eddington=[s[6 + d] / c2e if c2e > 0.0 else 0.0 for d in (0, 3, 5)])
+
+
+def moments_json(cycle: int, t: float, report: dict, integ: dict) -> str:
+    """One cycle's line of ``--moments FILE`` (examples/mcblock_amd writes the same characters: %.17g restores a
+    float's bits)."""
+    g = lambda x: "%.17g" % x                           # noqa: E731
+    lst = lambda xs: "[" + ", ".join(g(x) for x in xs) + "]"      # noqa: E731
+    return ("{" + f'"cycle": {int(cycle)}, "time": {g(t)}, "n_counted": {report["n_counted"]}, '
+            f'"n_skipped": {report["n_skipped"]}, "cells_nonempty": {report["cells_nonempty"]}, '
+            f'"longest_run": {report["longest_run"]}, "sorted": {report["sorted"]}, "n": {g(integ["n"])}, '
+            f'"e": {g(integ["e"])}, "w2": {g(integ["w2"])}, "f": {lst(integ["f"])}, "q": {lst(integ["q"])}, '
+            f'"eddington": {lst(integ["eddington"])}' + "}")
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m jaybenne_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -53,6 +83,10 @@ def main(argv=None) -> int:
     ap.add_argument("--ledger", default=None, metavar="FILE",
                     help="switch the energy ledger on: one JSON line per cycle to FILE, leak by face and the "
                          "residual of the energy balance on the per-cycle line, totals by face at the end")
+    ap.add_argument("--moments", default=None, metavar="FILE",
+                    help="after every cycle one JSON line to FILE: the report of EvaluateRadiationMoments and the "
+                         "domain integrals of count, energy, flux and second-moment tensor, with the Eddington "
+                         "factors (the deck key <jaybenne_amd> moments = true: to moments.jsonl)")
     ap.add_argument("overrides", nargs="*", help="block/key=value")
     args = ap.parse_args(argv)
 
@@ -73,6 +107,8 @@ def main(argv=None) -> int:
         return 2
     drv = mcblock.McblockDriver(pin, device=torch.device("cuda", 0), ledger=True if args.ledger else None)
     ledger_file = open(args.ledger, "w") if args.ledger else None
+    moments_path = args.moments or ("moments.jsonl" if pin.GetOrAddBoolean("jaybenne_amd", "moments", False) else None)
+    moments_file = open(moments_path, "w") if moments_path else None
     print(f"problem {drv.mcb.problem_id}: {drv.mesh.ndim}-D, {drv.mesh.nblocks} meshblocks, "
           f"levels {sorted(set(drv.mesh.blk_level.tolist()))}, {drv.md.n} photons")
     t0 = time.perf_counter()
@@ -96,6 +132,12 @@ def main(argv=None) -> int:
                 line += " leak=[" + ", ".join(f"{e:.6e}" for e in led["e_escaped"]) + f"] residual={led['residual']:.3e}"
             if drv.md.comb_history and drv.md.comb_history[-1]["cycle"] == drv.md.cycle:
                 line += f" combed={drv.md.comb_history[-1]['cells_combed']} new_ids={drv.md.comb_history[-1]['n_new_ids']}"
+            if moments_file is not None:
+                fields, rep = drv.jb.EvaluateRadiationMoments(drv.md)
+                integ = moments_integrals(fields.cpu().numpy(), np.asarray(drv.mesh.blk_dx)[drv.md.resident_gids],
+                                          drv.pkg.Param("speed_of_light"))
+                moments_file.write(moments_json(drv.md.cycle, drv.time, rep, integ) + "\n")
+                line += " eddington=[" + ", ".join(f"{e:.4f}" for e in integ["eddington"]) + "]"
             print(line)
     except JaybenneError as e:
         if not (checked and e.status == JB_ERR_INVARIANT):
@@ -104,6 +146,8 @@ def main(argv=None) -> int:
         print(f"TEST FAILED: {e}", file=sys.stderr)
         return 3
     print(f"walltime used = {time.perf_counter() - t0:.2f} s")
+    if moments_file is not None:
+        moments_file.close()
     if ledger_file is not None:
         ledger_file.close()
         import math

@@ -204,6 +204,19 @@ class CombReport(C.Structure):
     _fields_ = [("n_after", C.c_int64), ("n_new_ids", C.c_int64), ("e_after", C.c_double)]
 
 
+# jb_moments_report (include/jaybenne_amd.h): radiation moments; MOMENT_NAMES in the order of the enum JB_MOM_*
+JB_MOMENTS = 12
+MOMENT_NAMES = ("n", "e", "w2", "fx", "fy", "fz", "qxx", "qxy", "qxz", "qyy", "qyz", "qzz")
+
+
+class MomentsReport(C.Structure):
+    _fields_ = [("n_counted", C.c_int64), ("n_skipped", C.c_int64), ("cells_nonempty", C.c_int64),
+                ("longest_run", C.c_int64), ("sorted", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
 # jb_deposit_stats (include/jaybenne_amd.h): the counts of the last close of exact deposition
 class DepositStats(C.Structure):
     _fields_ = [("n_absorbed_addends", C.c_int64), ("n_census_addends", C.c_int64), ("n_truncated", C.c_int64),
@@ -268,6 +281,9 @@ PROTOTYPES = {
     "jb_release_scratch": (_int, [_vp]),
     "jb_comb_census_plan": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, _i64, C.c_uint32, C.POINTER(CombPlan)]),
     "jb_comb_census_apply": (_int, [_vp, _vp, C.POINTER(SwarmView), C.c_uint64, C.POINTER(CombReport)]),
+    "jb_moments_words": (_i64, [_vp]),
+    "jb_evaluate_radiation_moments": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, C.POINTER(MomentsReport)]),
+    "jb_evaluate_radiation_moments_host": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, C.POINTER(MomentsReport)]),
     "jb_defrag_policy": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, C.c_int32, C.POINTER(C.c_int32)]),
     "jb_pack_outgoing": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, _i64, _int, _vp, _i64, _vp]),
     "jb_unpack_incoming": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, _i64]),

@@ -29,6 +29,7 @@
 #include "jb_kernel_bsource.hpp"
 #include "jb_kernel_deposit.hpp"
 #include "jb_kernel_tilt.hpp"
+#include "jb_kernel_moments.hpp"
 #include "jb_select.hpp"
 
 using namespace jb;
@@ -91,6 +92,9 @@ struct jb_context {
   unsigned long long *step_gather_d = nullptr;
   size_t step_gather_words = 0;
   long long min_records = 0;  // JB_HANDOFF_MIN_RECORDS at jb_initialize: first size of those record buffers (tests)
+  // jb_evaluate_radiation_moments_host: the device array the fields pass through
+  double *moments_d = nullptr;
+  size_t moments_words = 0;
   // arithmetic of the gray IMC tracking step: lean (default) or exact (JB_EXACT_ARITH=1 in the
   // environment at jb_initialize, or jb_set_arithmetic)
   bool lean_arith = true;
@@ -593,6 +597,7 @@ extern "C" jb_status jb_finalize(jb_context *ctx) {
   if (ctx->ledger_gather_d) (void)hipFree(ctx->ledger_gather_d);
   if (ctx->bs_prefix_d) (void)hipFree(ctx->bs_prefix_d);
   if (ctx->bs_out_d) (void)hipFree(ctx->bs_out_d);
+  if (ctx->moments_d) (void)hipFree(ctx->moments_d);
   for (hipEvent_t e : ctx->tev) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->sort_ev) if (e) (void)hipEventDestroy(e);
   delete ctx;
@@ -2242,6 +2247,159 @@ extern "C" jb_status jb_comb_census_apply(jb_context *ctx, jb_mesh *mesh, jb_swa
   return comb_energy(ctx, S, n_after, c.epart, &out->e_after);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Radiation moments (jb_kernel_moments.hpp).  Scratch behind the sort's: the chunks' partial sums (two places of
+// kMomSums doubles per kMomChunk slots), the three counts of the report, the "out of order" flag.
+static_assert(kMoments == JB_MOMENTS && sizeof(jb_moments_report) == 40, "jb_limits.hpp restates the header");
+struct MomScratch {
+  unsigned *start, *key, *flag;
+  double *part;
+  unsigned long long *stats;
+  int sort_tiles;
+  size_t words;
+};
+static MomScratch mom_scratch(const jb_context *ctx, long long n, long long nbins) {
+  MomScratch m{};
+  m.sort_tiles = (int)((nbins + kScanTile - 1) / kScanTile);
+  size_t o = sort_scratch_words(ctx, n, nbins, m.sort_tiles);
+  const size_t opart = o; o += (size_t)kMomSums * 2 * (size_t)((n + kMomChunk - 1) / kMomChunk);
+  const size_t ostats = o; o += MS_N;
+  const size_t oflag = o; o += 1;
+  m.words = o;
+  unsigned long long *base = (unsigned long long *)ctx->scratch_d;
+  if (!base) return m;   // (asked for the size alone)
+  m.start = (unsigned *)(base + (size_t)kSortRecWords * (size_t)n);
+  m.key = m.start + nbins + m.sort_tiles;
+  m.part = (double *)(base + opart);
+  m.stats = base + ostats;
+  m.flag = (unsigned *)(base + oflag);
+  return m;
+}
+// lanes per cell of k_mom_cells: the power of two that holds about twice the mean run and two more
+static int mom_group(long long n, long long cells) {
+  if (const char *e = getenv("JB_MOMENTS_GROUP")) {
+    const int g = atoi(e);
+    if (g >= 1 && g <= 64 && (g & (g - 1)) == 0) return g;
+  }
+  const double target = 2.0 * (double)n / (double)(cells > 0 ? cells : 1) + 2.0;
+  int g = 1;
+  while (g < 64 && (double)g < target) g *= 2;
+  return g;
+}
+
+extern "C" int64_t jb_moments_words(const jb_mesh *mesh) {
+  return mesh ? (int64_t)JB_MOMENTS * (int64_t)mesh->dm.nblocks * (int64_t)mesh->dm.ncell : 0;
+}
+
+extern "C" jb_status jb_evaluate_radiation_moments(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
+                                                   double *out_dev, jb_moments_report *report) {
+  JB_RANGE("Jaybenne::EvaluateRadiationMoments");
+  if (!ctx || !mesh || !out_dev) return fail(JB_ERR_INVALID, "jb_evaluate_radiation_moments: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  jb_status st = check_swarm(swarm, "jb_evaluate_radiation_moments");
+  if (st != JB_COMPLETE) return st;
+  const long long n = swarm->n;
+  if (n >= (1ll << 32)) return fail(JB_ERR_INVALID, "jb_evaluate_radiation_moments: more than 2^32 - 1 particles");
+  const DevMesh &M = mesh->dm;
+  const unsigned long long nkeys64 = (unsigned long long)M.nblocks * (unsigned long long)M.ntot;
+  if (nkeys64 >= (1ull << 32) - 1ull) return fail(JB_ERR_INVALID, "jb_evaluate_radiation_moments: more than 2^32 - 2 cells");
+  const unsigned nkeys = (unsigned)nkeys64;
+  const long long nbins = (long long)nkeys + 1;
+  const long long cells = (long long)M.nblocks * M.ncell;
+  if (report) memset(report, 0, sizeof *report);
+  // (all of the scratch first: the sort then finds room, and a failed allocation leaves the swarm as it was)
+  st = ensure_scratch(ctx, mom_scratch(ctx, n, nbins).words, /*slack=*/false);
+  if (st != JB_COMPLETE) return st;
+  ctx->comb.valid = false;   // (a comb plan not yet applied lived in this memory)
+  const MomScratch m = mom_scratch(ctx, n, nbins);
+  const DevSwarm S = dev_swarm(swarm);
+  const int gn = grid_for(ctx, n);
+  // In order already?  As jb_comb_census_plan asks: key order under JB_CELL_ORDER_ANY, the canonical order -- whose
+  // sort makes that test itself -- under JB_CELL_ORDER_BY_ID.
+  const bool by_id = ctx->cell_order == JB_CELL_ORDER_BY_ID;
+  unsigned unsorted = 0u;
+  if (n > 0 && by_id) {
+    int moved = 0;
+    st = order_sort(ctx, mesh, swarm, nbins, m.sort_tiles, &moved);
+    if (st != JB_COMPLETE) return st;
+    unsorted = moved ? 1u : 0u;
+  } else if (n > 0) {
+    // (one pass makes the keys and the histogram the cells' bounds come from; a swarm in order needs no second)
+    JB_HIP(hipMemsetAsync(m.flag, 0, sizeof(unsigned), ctx->stream));
+    JB_HIP(hipMemsetAsync(m.start, 0, sizeof(unsigned) * (size_t)nbins, ctx->stream));
+    hipLaunchKernelGGL(k_sort_count, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, m.key, m.start);
+    hipLaunchKernelGGL(k_comb_unsorted, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)m.key, n, m.flag);
+    JB_HIP(hipGetLastError());
+    JB_HIP(hipMemcpyAsync(&unsorted, m.flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    JB_HIP(hipStreamSynchronize(ctx->stream));
+    if (unsorted) {
+      st = jb_defrag_particles(ctx, mesh, swarm);
+      if (st != JB_COMPLETE) return st;
+    }
+  }
+  if (unsorted) {   // for the schedule of jb_defrag_policy this is a sort, as a comb plan that sorted is
+    ctx->rate_ref = 0.0;
+    ctx->rate_before_sort = 0.0;
+    ctx->excess_ms = 0.0;
+    ctx->cycles_since_sort = 0;
+  }
+  // the cells' bounds: the histogram of the keys of the swarm as it lies now, and its scan (what a move left in
+  // the histogram's place are the cells' ends, not their starts)
+  JB_HIP(hipMemsetAsync(m.stats, 0, sizeof(unsigned long long) * MS_N, ctx->stream));
+  const bool counted = n > 0 && !by_id && !unsorted;   // the histogram of the order test stands
+  if (!counted) JB_HIP(hipMemsetAsync(m.start, 0, sizeof(unsigned) * (size_t)nbins, ctx->stream));
+  if (n > 0) {
+    unsigned *sums = m.start + nbins;
+    if (!counted)
+      hipLaunchKernelGGL(k_sort_count, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, m.key, m.start);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(m.sort_tiles), dim3(kBlock), 0, ctx->stream, m.start, nbins, sums);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums, m.sort_tiles);
+    hipLaunchKernelGGL(k_scan_add, dim3(m.sort_tiles), dim3(kBlock), 0, ctx->stream, m.start, nbins, (const unsigned *)sums);
+  }
+  const int G = mom_group(n, cells);
+  // (one workgroup per 256 slots, not a grid capped to the chip: chunk heads lie 64 waves apart in a long run, and
+  // a strided walk would hand all of them to the same few waves; the hardware deals workgroups out as others end)
+  if (n > 0)
+    hipLaunchKernelGGL(k_mom_chunks, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, (const unsigned *)m.key,
+                       (const unsigned *)m.start, (unsigned)G, m.part, out_dev);
+  const int gc = grid_for(ctx, cells);
+  with_int<1, 2, 4, 8, 16, 32, 64>(G, [&](auto g) {
+    hipLaunchKernelGGL(k_mom_cells<decltype(g)::value>, dim3(gc), dim3(kBlock), 0, ctx->stream, M, S,
+                       (const unsigned *)m.start, (const double *)m.part, out_dev, m.stats);
+  });
+  JB_HIP(hipGetLastError());
+  if (report) {
+    unsigned long long stats[MS_N] = {};
+    JB_HIP(hipMemcpyAsync(stats, m.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
+    JB_HIP(hipStreamSynchronize(ctx->stream));
+    report->n_counted = (int64_t)stats[MS_COUNTED];
+    report->n_skipped = (int64_t)n - report->n_counted;
+    report->cells_nonempty = (int64_t)stats[MS_NONEMPTY];
+    report->longest_run = (int64_t)stats[MS_LONGEST];
+    report->sorted = unsorted ? 1 : 0;
+  }
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_evaluate_radiation_moments_host(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
+                                                        double *out_host, jb_moments_report *report) {
+  if (!ctx || !mesh || !out_host) return fail(JB_ERR_INVALID, "jb_evaluate_radiation_moments_host: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  const size_t words = (size_t)jb_moments_words(mesh);
+  if (words > ctx->moments_words) {
+    if (ctx->moments_d) JB_HIP(hipFree(ctx->moments_d));
+    ctx->moments_d = nullptr;
+    ctx->moments_words = 0;
+    JB_HIP(hipMalloc(&ctx->moments_d, words * sizeof(double)));
+    ctx->moments_words = words;
+  }
+  const jb_status st = jb_evaluate_radiation_moments(ctx, mesh, swarm, ctx->moments_d, report);
+  if (st != JB_COMPLETE) return st;
+  JB_HIP(hipMemcpyAsync(out_host, ctx->moments_d, words * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  return JB_COMPLETE;
+}
+
 // the sort of jb_defrag_policy, timed, and the policy's state behind it
 static jb_status defrag_now(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, double rate, int32_t *sorted) {
   if (!ctx->sort_ev[0]) {
@@ -2289,6 +2447,9 @@ extern "C" jb_status jb_release_scratch(jb_context *ctx) {
   ctx->step_send_cap = ctx->step_recv_cap = 0;
   ctx->step_gather_d = nullptr;
   ctx->step_gather_words = 0;
+  if (ctx->moments_d) JB_HIP(hipFree(ctx->moments_d));
+  ctx->moments_d = nullptr;
+  ctx->moments_words = 0;
   return JB_COMPLETE;
 }
 

@@ -262,6 +262,10 @@ class MeshData:
         self.comb_trigger = 0
         self.comb_history: list = []                # one dict per cycle whose comb changed the swarm
         self._comb_sorted = False                   # the last plan sorted the swarm
+        # radiation moments (EvaluateRadiationMoments; include/jaybenne_amd.h: jb_evaluate_radiation_moments): the
+        # last call's device tensor (12, nblocks, nx3, nx2, nx1) and report; None until a host asks
+        self.moments: Optional[torch.Tensor] = None
+        self.moments_report: Optional[dict] = None
         # exact deposition (md.deposition; include/jaybenne_amd.h: jb_set_deposition): one record per cycle, the
         # counts of its close on this rank (jb_deposit_stats) and the cycle
         self.deposit_history: list = []
@@ -795,6 +799,36 @@ def EvaluateRadiationEnergy(md: MeshData) -> TaskStatus:
     _lib.check(md.lib.jb_evaluate_radiation_energy(md.pkg.ctx, md.handle, C.byref(md.sv)))
     _sum_over_ranks(md, ("tally",))
     return TaskStatus.complete
+
+
+def EvaluateRadiationMoments(md: MeshData):
+    """Per-cell count, energy density, sum of squared weights, flux and second-moment tensor of the census (the
+    reference has no such task; include/jaybenne_amd.h: ``jb_evaluate_radiation_moments``).  Returns ``(moments,
+    report)``: a device tensor of shape ``(12, nblocks, nx3, nx2, nx1)`` in the order of ``_lib.MOMENT_NAMES`` over
+    the resident blocks (zeros in halo copies), also kept as ``md.moments``, and the call's report as a dict.  The
+    call sorts the swarm by (block, cell) when it is not in that order.  On a replicated mesh every rank holds a
+    share of every cell's photons and every component is linear in the photons: the ranks' tensors are summed with
+    the all-reduce the tally uses (and the counts of the report over the ranks).  On a block partition a cell's
+    photons are on its owner and nothing is reduced."""
+    md._sync_stream()
+    nx = md.mesh.nx
+    shape = (_lib.JB_MOMENTS, md.nblocks, int(nx[2]), int(nx[1]), int(nx[0]))
+    if md.moments is None or tuple(md.moments.shape) != shape:
+        md.moments = torch.empty(shape, dtype=torch.float64, device=md.device)
+    assert md.moments.numel() == int(md.lib.jb_moments_words(md.handle))
+    rep = _lib.MomentsReport()
+    _lib.check(md.lib.jb_evaluate_radiation_moments(md.pkg.ctx, md.handle, C.byref(md.sv), md.moments.data_ptr(),
+                                                    C.byref(rep)))
+    report = rep.as_dict()
+    if md.replicated:
+        md.comm.allreduce_sum_tensor(md.moments)
+        keys = ("n_counted", "n_skipped")
+        total = md.comm.allreduce_sum_int64(np.array([report[k] for k in keys], dtype=np.int64))
+        report.update({k: int(v) for k, v in zip(keys, total)})
+        report["cells_nonempty"] = int((md.moments[0] > 0).sum().item())
+        report["longest_run"] = int(md.moments[0].max().item()) if md.moments[0].numel() else 0
+    md.moments_report = report
+    return md.moments, report
 
 
 def UpdateFluid(md: MeshData) -> TaskStatus:
