@@ -596,6 +596,12 @@ int main(int argc, char **argv) {
       const std::string tilt = pin.GetOrAddString("jaybenne_amd", "source_tilt", "");
       if (!tilt.empty()) jb::SetSourceTilt(&md, jb::SourceTiltOf(tilt));
     }
+    // (as the Python driver: source_allocation = energy -- photon numbers proportional to the energy a cell sources;
+    // without the key the library's default, which JB_SOURCE_ALLOCATION sets)
+    {
+      const std::string alloc = pin.GetOrAddString("jaybenne_amd", "source_allocation", "");
+      if (!alloc.empty()) jb::SetSourceAllocation(&md, jb::SourceAllocationOf(alloc));
+    }
     // (as the Python driver: the boundary source -- a black wall of temperature bsource_<face>_temperature behind a
     // domain face, bsource_num_particles photons per cycle over all such faces; every temperature 0 = off)
     md.bsource_num_particles = pin.GetOrAddInteger("jaybenne_amd", "bsource_num_particles", 0);

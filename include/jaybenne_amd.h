@@ -926,6 +926,58 @@ int jb_get_source_tilt(const jb_context *ctx);
  * JB_ERR_INVALID if that call was not made under JB_TILT_LINEAR (or none was made), or for a halo copy. */
 jb_status jb_source_tilt_slopes(jb_context *ctx, const jb_mesh *mesh, int local_block, double *out_host);
 
+/* ---- source allocation -- how many of a source call's photons a cell gets (jaybenne_amd/csrc/jb_kernel_salloc.hpp).
+ * The reference's `uniform` strategy gives every cell the same number whatever it sources (sourcing.cpp:68-69,
+ * 99-103): a cold cell's photons carry almost no energy, yet each costs a full history.  Its `energy` strategy is
+ * declared and rejected (sourcing.cpp:38), and <jaybenne> source_strategy = energy STAYS rejected by every call
+ * here.  Under JB_ALLOC_ENERGY (an extension: <jaybenne_amd> source_allocation = energy) a cell's photon number is
+ * proportional to the energy it sources, so the new photons carry nearly equal weights.  A source call, thermal or
+ * emission, with N = params.num_particles -- the target for the WHOLE mesh and the whole call; blocks_in_call and
+ * the npc of sourcing.cpp:68-69 play no part -- then does:
+ *   1. Energy pass (jb_source_energy_sums).  For every interior cell of every owned resident block, erad with the
+ *      very expressions and product order of the uniform count -- thermal ((4 sb / c) (T^2 T^2)) dv, emission
+ *      ((fleck j) dv) dt -- stored in the src_ew field, which stages it between the two kernels so that both see
+ *      the same bits.  Per block e_block[b]: thread t of 256 starts from +0.0 and adds cells t, t + 256, ... of the
+ *      (k, j, i) order in rising order; then s[t] += s[t + d] for t < d, d = 128, 64, ... 1; e_block = s[0].  No
+ *      floating-point atomics.  A halo copy gives 0.
+ *   2. Total (jb_source_energy_total).  E_tot = the sum of e_block over the GLOBAL block ids in rising order,
+ *      sequentially from +0.0: the same bits on every rank and for every partition.  scale = (double)N / E_tot,
+ *      one division on the host.  A non-finite (or negative) E_tot, or a scale that is not finite, is
+ *      JB_ERR_INVALID; E_tot == 0 sources nothing and completes (every count 0, every weight 0).
+ *   3. Count pass (jb_source_photons_count_energy).  Per cell nu = erad scale; f = floor(nu);
+ *      n = f + (double)((nu - f) > xi), xi the ONE draw of the cell's rounding stream -- the stream, epoch and
+ *      draw of the uniform count; src_num = n; src_ew = erad / n when f >= 1 (the cell's energy is sourced
+ *      exactly), erad / nu when f = 0 and n = 1 (unbiased roulette, about E_tot / N), 0 when n = 0.  Then the
+ *      block's exclusive prefix and count as the uniform count forms them.  An N for which a block's count could
+ *      pass 2^31 - 1 (N + cells per block) is JB_ERR_INVALID before any launch.
+ *   4. energy_delta.  The emission source's fill sets energy_delta = -(n src_ew), one product, by a kernel of its
+ *      own (the uniform path's serial loop over a cell's photons would run up to N times in one thread);
+ *      set_energy_delta = 0 keeps its meaning.
+ *   5. Fill.  jb_source_photons_fill / _fill_range are as they were: they read prefix, src_ew and the ids; the
+ *      tilt's slopes are still written behind the count; the boundary source keeps its own N_b.
+ * jb_source_photons_count in this mode runs 1-3 in a row when the mesh view is wholly resident and owned (one rank,
+ * or a rank of a replicated mesh) -- the path jb_radiation_step takes; otherwise JB_ERR_INVALID, naming the calls
+ * below, between which the host gathers every rank's block sums (each block has one owner: jaybenne_amd/jaybenne.py
+ * sends them as bit patterns through an integer sum).  jb_radiation_step_ranks is outside this mode: under
+ * JB_ALLOC_ENERGY it returns JB_ERR_UNSUPPORTED on every rank before its first collective (the mode is a property
+ * of the call that all ranks share); examples/handoff_mpi and the Parthenon adapter do not set it.
+ * With JB_ALLOC_UNIFORM (the default) no kernel of jb_kernel_salloc.hpp is launched and every call gives the bits it
+ * gave.  JB_SOURCE_ALLOCATION=energy in the environment makes ENERGY the default of jb_initialize, like
+ * JB_SOURCE_TILT. */
+enum { JB_ALLOC_UNIFORM = 0, JB_ALLOC_ENERGY = 1 };
+jb_status jb_set_source_allocation(jb_context *ctx, int mode);
+int jb_get_source_allocation(const jb_context *ctx);
+/* Step 1: e_block_host[b] for the mesh view's resident blocks b (0 for a halo copy; all 0 and no launch for the
+ * emission source without do_emission).  Synchronises the context's stream.  JB_ERR_INVALID outside ENERGY mode. */
+jb_status jb_source_energy_sums(jb_context *ctx, jb_mesh *mesh, int source_type, double dt, double *e_block_host);
+/* Step 2: the sum of e_block_by_gid[0 .. nblocks_total) in rising order from +0.0 -- host code, so that every host
+ * adds alike. */
+double jb_source_energy_total(const double *e_block_by_gid, int nblocks_total);
+/* Step 3, for the energies the mesh's last jb_source_energy_sums call of this source_type staged (JB_ERR_INVALID
+ * without one since the mesh's last count); nper_block_host / prefix_dev as jb_source_photons_count. */
+jb_status jb_source_photons_count_energy(jb_context *ctx, jb_mesh *mesh, int source_type, double dt, uint32_t epoch,
+                                         double e_total, int32_t *nper_block_host, int32_t *prefix_dev);
+
 /* ---- transport invariants (checked library) -- the reference's PARTHENON_DEBUG_REQUIREs of the
  * tracking loop and of SampleDDMCBlockFace, evaluated on every pass (jaybenne_amd/csrc/jb_invariants.hpp).
  * `make -C jaybenne_amd/csrc checked` builds libjaybenne_amd_checked.so from the same sources with

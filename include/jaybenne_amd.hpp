@@ -703,6 +703,19 @@ inline int SourceTiltOf(const std::string &value) {
   if (value == "linear") return JB_TILT_LINEAR;
   throw std::invalid_argument("jaybenne_amd/source_tilt = '" + value + "': one of none, linear");
 }
+// source allocation: JB_ALLOC_UNIFORM (default: every cell the same number of new photons, sourcing.cpp:68-69) or
+// JB_ALLOC_ENERGY -- a cell's number follows the energy it sources, num_particles over the whole mesh per call, so
+// the new photons carry nearly equal weights (jaybenne_amd.h: jb_set_source_allocation).  This MeshData holds the
+// whole mesh, so SourcePhotons and RadiationStep need nothing else: jb_source_photons_count runs the energy pass, the
+// total and the count pass in a row.
+inline void SetSourceAllocation(MeshData *md, int mode) { Check(jb_set_source_allocation(md->ctx(), mode)); }
+inline int GetSourceAllocation(MeshData *md) { return jb_get_source_allocation(md->ctx()); }
+// the mode of the deck key <jaybenne_amd> source_allocation = uniform | energy
+inline int SourceAllocationOf(const std::string &value) {
+  if (value == "uniform") return JB_ALLOC_UNIFORM;
+  if (value == "energy") return JB_ALLOC_ENERGY;
+  throw std::invalid_argument("jaybenne_amd/source_allocation = '" + value + "': one of uniform, energy");
+}
 inline Real EstimateTimestepMesh(MeshData *md) { return jb_estimate_timestep(md->ctx()); }
 
 // jaybenne::InitializeRadiation(mbd, is_thermal) -- jaybenne.cpp:570-578

@@ -53,6 +53,7 @@ ARITH_EXACT, ARITH_LEAN = 0, 1   # enum of jb_set_arithmetic
 CELL_ORDER_ANY, CELL_ORDER_BY_ID = 0, 1   # enum of jb_set_cell_order
 DEPOSIT_ATOMIC, DEPOSIT_EXACT = 0, 1      # enum of jb_set_deposition
 TILT_NONE, TILT_LINEAR = 0, 1             # enum of jb_set_source_tilt
+ALLOC_UNIFORM, ALLOC_ENERGY = 0, 1        # enum of jb_set_source_allocation
 JB_DEPOSIT_ABSORBED, JB_DEPOSIT_ARRIVALS = 1, 2   # what jb_deposit_accumulate sweeps for (a sum of them)
 
 FIELD_IDS = {"rho": 0, "sie": 1, "u": 2, "fleck": 3, "tally": 4, "edelta": 5}   # enum jb_field
@@ -330,6 +331,11 @@ PROTOTYPES = {
     "jb_set_source_tilt": (_int, [_vp, _int]),
     "jb_get_source_tilt": (_int, [_vp]),
     "jb_source_tilt_slopes": (_int, [_vp, _vp, _int, _vp]),
+    "jb_set_source_allocation": (_int, [_vp, _int]),
+    "jb_get_source_allocation": (_int, [_vp]),
+    "jb_source_energy_sums": (_int, [_vp, _vp, _int, C.c_double, _vp]),
+    "jb_source_energy_total": (C.c_double, [_vp, _int]),
+    "jb_source_photons_count_energy": (_int, [_vp, _vp, _int, C.c_double, C.c_uint32, C.c_double, _vp, _vp]),
     "jb_debug_math": (_int, [_vp, _int, _vp, _int, _vp]),
     "jb_debug_model_coefficients": (_int, [_vp, C.POINTER(C.c_double * 4)]),
     "jb_debug_model_eval": (_int, [_vp, _int, _vp, _int, _vp]),

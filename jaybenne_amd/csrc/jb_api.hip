@@ -29,6 +29,7 @@
 #include "jb_kernel_bsource.hpp"
 #include "jb_kernel_deposit.hpp"
 #include "jb_kernel_tilt.hpp"
+#include "jb_kernel_salloc.hpp"
 #include "jb_kernel_moments.hpp"
 #include "jb_select.hpp"
 
@@ -148,6 +149,9 @@ struct jb_context {
   bool dep_has_last = false;
   // source tilt (jb_set_source_tilt; JB_SOURCE_TILT=linear at jb_initialize; jb_kernel_tilt.hpp): off by default
   int source_tilt = JB_TILT_NONE;
+  // source allocation (jb_set_source_allocation; JB_SOURCE_ALLOCATION=energy at jb_initialize; jb_kernel_salloc.hpp):
+  // uniform by default
+  int source_allocation = JB_ALLOC_UNIFORM;
 };
 constexpr int kLedgerHead = 64;   // words in front of the partial sums (LW_N of them used)
 constexpr int kLedgerWords = (int)(sizeof(jb_energy_ledger) / 8);
@@ -206,6 +210,10 @@ struct jb_mesh {
   double *tilt_d = nullptr;
   bool tilt_valid = false;
   std::vector<uint8_t> owned_host;
+  // source allocation: the mesh's last count call was made under JB_ALLOC_ENERGY (the fill then sets energy_delta
+  // by k_salloc_edelta), and the last jb_source_energy_sums call's source type (-1: none since the last count)
+  bool salloc_last = false;
+  int salloc_sums_type = -1;
 };
 // open / closed: the context knows the meshes whose accumulators are open (jb_set_deposition turns a change of mode
 // down while there is one, jb_remove_marked_particles keeps their swarm's n, jb_finalize lets go of them)
@@ -493,6 +501,8 @@ extern "C" jb_status jb_initialize(const jb_params *params, const jb_eos *eos,
   if (const char *e = getenv("JB_CELL_ORDER")) ctx->cell_order = strcmp(e, "id") == 0 ? JB_CELL_ORDER_BY_ID : JB_CELL_ORDER_ANY;
   if (const char *e = getenv("JB_DEPOSITION")) ctx->deposition = strcmp(e, "exact") == 0 ? JB_DEPOSIT_EXACT : JB_DEPOSIT_ATOMIC;
   if (const char *e = getenv("JB_SOURCE_TILT")) ctx->source_tilt = strcmp(e, "linear") == 0 ? JB_TILT_LINEAR : JB_TILT_NONE;
+  if (const char *e = getenv("JB_SOURCE_ALLOCATION"))
+    ctx->source_allocation = strcmp(e, "energy") == 0 ? JB_ALLOC_ENERGY : JB_ALLOC_UNIFORM;
   if (const char *e = getenv("JB_TRANSPORT_BLOCKS_PER_CU")) ctx->blocks_per_cu_env = atoi(e);
   if (const char *e = getenv("JB_NO_DDMC_ALL")) ctx->no_ddmc_all = e[0] == '1';
   if (const char *e = getenv("JB_NO_IMC_CELL")) ctx->no_imc_cell = e[0] == '1';
@@ -1017,6 +1027,8 @@ extern "C" jb_status jb_update_derived_transport_fields(jb_context *ctx, jb_mesh
   return JB_COMPLETE;
 }
 
+static jb_status source_count_finish(jb_context *ctx, jb_mesh *mesh, int *nper_d, int32_t *nper_block_host);
+
 extern "C" jb_status jb_source_photons_count(jb_context *ctx, jb_mesh *mesh, int source_type,
                                              double dt, int blocks_in_call, uint32_t epoch,
                                              int32_t *nper_block_host, int32_t *prefix_dev) {
@@ -1032,6 +1044,23 @@ extern "C" jb_status jb_source_photons_count(jb_context *ctx, jb_mesh *mesh, int
     for (int b = 0; b < M.nblocks; ++b) nper_block_host[b] = 0;
     return JB_COMPLETE;
   }
+  if (ctx->source_allocation == JB_ALLOC_ENERGY) {
+    // (source allocation: energy pass, total, count pass in a row -- only where this rank sees every block's sum)
+    if (M.nblocks != M.nblocks_total || mesh->nowned != M.nblocks_total)
+      return fail(JB_ERR_INVALID, "jb_source_photons_count: source allocation is energy and the mesh is not wholly "
+                  "resident and owned (%d of %d blocks owned here): call jb_source_energy_sums, add the block sums of "
+                  "all ranks by jb_source_energy_total, then jb_source_photons_count_energy", mesh->nowned,
+                  M.nblocks_total);
+    std::vector<double> e_local((size_t)M.nblocks), e_gid((size_t)M.nblocks_total, 0.0);
+    jb_status st = jb_source_energy_sums(ctx, mesh, source_type, dt, e_local.data());
+    if (st != JB_COMPLETE) return st;
+    for (int b = 0; b < M.nblocks; ++b) e_gid[(size_t)mesh->gid_host[(size_t)b]] = e_local[(size_t)b];
+    return jb_source_photons_count_energy(ctx, mesh, source_type, dt, epoch,
+                                          jb_source_energy_total(e_gid.data(), M.nblocks_total), nper_block_host,
+                                          prefix_dev);
+  }
+  mesh->salloc_last = false;
+  mesh->salloc_sums_type = -1;
   if (blocks_in_call < 1) return fail(JB_ERR_INVALID, "blocks_in_call must be >= 1");
   jb_status st = ensure_scratch(ctx, (size_t)M.nblocks);
   if (st != JB_COMPLETE) return st;
@@ -1042,6 +1071,12 @@ extern "C" jb_status jb_source_photons_count(jb_context *ctx, jb_mesh *mesh, int
   hipLaunchKernelGGL(k_source_count, dim3(M.nblocks), dim3(kBlock), 0, ctx->stream, M, ctx->dp,
                      source_type, dt, npc, epoch, nper_d, prefix_dev);
   JB_HIP(hipGetLastError());
+  return source_count_finish(ctx, mesh, nper_d, nper_block_host);
+}
+
+// what follows the count kernel, whichever allocation it counted by: the tilt's slopes, the counts to the host
+static jb_status source_count_finish(jb_context *ctx, jb_mesh *mesh, int *nper_d, int32_t *nper_block_host) {
+  const DevMesh &M = mesh->dm;
   // (source tilt: the slopes of T^4 this call's photons are placed by, from the state the count read)
   mesh->tilt_valid = false;
   if (ctx->source_tilt == JB_TILT_LINEAR) {
@@ -1121,8 +1156,12 @@ extern "C" jb_status jb_source_photons_fill_range(jb_context *ctx, jb_mesh *mesh
                         ctx->stream));
   // (set_energy_delta = 0: energy_delta := 0 instead of minus the emitted energy -- every rank of a
   // replicated-mesh run but one, so that the sum over ranks carries the emission once)
-  hipLaunchKernelGGL(k_source_edelta, dim3(grid_for(ctx, (long long)M.nblocks * M.ncell)),
-                     dim3(kBlock), 0, ctx->stream, M, set_energy_delta ? source_type : 0);
+  if (!mesh->salloc_last)
+    hipLaunchKernelGGL(k_source_edelta, dim3(grid_for(ctx, (long long)M.nblocks * M.ncell)),
+                       dim3(kBlock), 0, ctx->stream, M, set_energy_delta ? source_type : 0);
+  else   // (source allocation: one product per cell; k_source_edelta's loop runs once per photon of the cell)
+    hipLaunchKernelGGL(k_salloc_edelta, dim3(grid_for(ctx, (long long)M.nblocks * M.ncell)),
+                       dim3(kBlock), 0, ctx->stream, M, set_energy_delta ? source_type : 0);
   if (total > 0 && !tilted)
     hipLaunchKernelGGL(k_source_fill, dim3(grid_for(ctx, total)), dim3(kBlock), 0, ctx->stream, M,
                        ctx->dp, dev_swarm(swarm), source_type, t_start, dt, (const int *)prefix_dev,
@@ -1182,6 +1221,107 @@ extern "C" jb_status jb_source_tilt_slopes(jb_context *ctx, const jb_mesh *mesh,
                         ctx->stream));
   JB_HIP(hipStreamSynchronize(ctx->stream));
   return JB_COMPLETE;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The source allocation (jb_kernel_salloc.hpp): under JB_ALLOC_ENERGY a cell's photon number follows its energy.
+extern "C" jb_status jb_set_source_allocation(jb_context *ctx, int mode) {
+  if (!ctx || (mode != JB_ALLOC_UNIFORM && mode != JB_ALLOC_ENERGY))
+    return fail(JB_ERR_INVALID, "jb_set_source_allocation: mode = %d is neither JB_ALLOC_UNIFORM nor JB_ALLOC_ENERGY", mode);
+  ctx->source_allocation = mode;
+  return JB_COMPLETE;
+}
+extern "C" int jb_get_source_allocation(const jb_context *ctx) {
+  return ctx && ctx->source_allocation == JB_ALLOC_ENERGY ? JB_ALLOC_ENERGY : JB_ALLOC_UNIFORM;
+}
+
+// a cell's nu is at most N (1 + a few ulp), so a block's count stays below N + its cells: that must fit an int32
+static jb_status salloc_check_target(const jb_context *ctx, const DevMesh &M) {
+  const long long n_target = (long long)ctx->params.num_particles;
+  if (n_target < 0 || n_target + (long long)M.ncell > 2147483647ll)
+    return fail(JB_ERR_INVALID, "source allocation energy: num_particles = %lld plus the %d cells of a block passes "
+                "2^31 - 1, the most a block's count can hold", n_target, M.ncell);
+  return JB_COMPLETE;
+}
+
+extern "C" double jb_source_energy_total(const double *e_block_by_gid, int nblocks_total) {
+  double e = 0.0;
+  for (int g = 0; e_block_by_gid && g < nblocks_total; ++g) e += e_block_by_gid[g];
+  return e;
+}
+
+extern "C" jb_status jb_source_energy_sums(jb_context *ctx, jb_mesh *mesh, int source_type, double dt,
+                                           double *e_block_host) {
+  JB_RANGE("Jaybenne::SourceEnergySums");
+  if (!ctx || !mesh || !e_block_host) return fail(JB_ERR_INVALID, "jb_source_energy_sums: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  if (ctx->params.source_strategy == JB_STRATEGY_ENERGY)
+    return fail(JB_ERR_INVALID, "Energy source strategy not implemented!");  // sourcing.cpp:38
+  if (ctx->source_allocation != JB_ALLOC_ENERGY)
+    return fail(JB_ERR_INVALID, "jb_source_energy_sums: source allocation is not energy (jb_set_source_allocation)");
+  if (source_type != JB_SOURCE_THERMAL && source_type != JB_SOURCE_EMISSION)
+    return fail(JB_ERR_INVALID, "jb_source_energy_sums: source_type = %d", source_type);
+  const DevMesh &M = mesh->dm;
+  mesh->salloc_sums_type = -1;
+  if (source_type == JB_SOURCE_EMISSION && !ctx->params.do_emission) {  // sourcing.cpp:41-43
+    for (int b = 0; b < M.nblocks; ++b) e_block_host[b] = 0.0;
+    return JB_COMPLETE;
+  }
+  jb_status st = salloc_check_target(ctx, M);
+  if (st != JB_COMPLETE) return st;
+  st = ensure_scratch(ctx, (size_t)M.nblocks);
+  if (st != JB_COMPLETE) return st;
+  double *e_d = (double *)ctx->scratch_d;
+  hipLaunchKernelGGL(k_salloc_energy, dim3(M.nblocks), dim3(kBlock), 0, ctx->stream, M, ctx->dp, source_type, dt, e_d);
+  JB_HIP(hipGetLastError());
+  JB_HIP(hipMemcpyAsync(e_block_host, e_d, sizeof(double) * M.nblocks, hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  mesh->salloc_sums_type = source_type;
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_source_photons_count_energy(jb_context *ctx, jb_mesh *mesh, int source_type, double dt,
+                                                    uint32_t epoch, double e_total, int32_t *nper_block_host,
+                                                    int32_t *prefix_dev) {
+  JB_RANGE("Jaybenne::SourcePhotons1");
+  (void)dt;   // (the energies are those jb_source_energy_sums staged)
+  if (!ctx || !mesh || !nper_block_host || !prefix_dev)
+    return fail(JB_ERR_INVALID, "jb_source_photons_count_energy: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  if (ctx->params.source_strategy == JB_STRATEGY_ENERGY)
+    return fail(JB_ERR_INVALID, "Energy source strategy not implemented!");  // sourcing.cpp:38
+  if (ctx->source_allocation != JB_ALLOC_ENERGY)
+    return fail(JB_ERR_INVALID, "jb_source_photons_count_energy: source allocation is not energy "
+                "(jb_set_source_allocation)");
+  if (epoch >= (1u << 20))  // cell_stream_id keeps the source-call counter in 20 bits
+    return fail(JB_ERR_INVALID, "more than 2^20 source calls: the per-cell rounding streams would repeat");
+  const DevMesh &M = mesh->dm;
+  if (source_type == JB_SOURCE_EMISSION && !ctx->params.do_emission) {  // sourcing.cpp:41-43
+    for (int b = 0; b < M.nblocks; ++b) nper_block_host[b] = 0;
+    return JB_COMPLETE;
+  }
+  if (mesh->salloc_sums_type != source_type)
+    return fail(JB_ERR_INVALID, "jb_source_photons_count_energy: no jb_source_energy_sums call of source type %d "
+                "on this mesh since its last count", source_type);
+  mesh->salloc_sums_type = -1;   // (the count overwrites the staged energies with the weights)
+  const long long n_target = (long long)ctx->params.num_particles;
+  jb_status st = salloc_check_target(ctx, M);
+  if (st != JB_COMPLETE) return st;
+  if (!std::isfinite(e_total) || e_total < 0.0)
+    return fail(JB_ERR_INVALID, "source allocation energy: the total energy to source is %g", e_total);
+  // E_tot = 0: nothing to source -- scale = 0 gives every cell nu = 0, no photon and weight 0
+  const double scale = e_total > 0.0 ? (double)n_target / e_total : 0.0;
+  if (!std::isfinite(scale))
+    return fail(JB_ERR_INVALID, "source allocation energy: num_particles / E_tot = %lld / %g is not finite", n_target,
+                e_total);
+  st = ensure_scratch(ctx, (size_t)M.nblocks);
+  if (st != JB_COMPLETE) return st;
+  int *nper_d = (int *)ctx->scratch_d;
+  hipLaunchKernelGGL(k_salloc_count, dim3(M.nblocks), dim3(kBlock), 0, ctx->stream, M, ctx->dp, scale, epoch, nper_d,
+                     prefix_dev);
+  JB_HIP(hipGetLastError());
+  mesh->salloc_last = true;
+  return source_count_finish(ctx, mesh, nper_d, nper_block_host);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3454,6 +3594,9 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
     return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: %d ranks need a transport with both collectives", nranks);
   if (!ctx || !mesh || !swarm || !next_id || !cycle)
     return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: null argument");
+  if (ctx->source_allocation == JB_ALLOC_ENERGY)   // (the mode is a property of the call that all ranks share)
+    return fail(JB_ERR_UNSUPPORTED, "jb_radiation_step_ranks: source allocation energy is not driven by this call "
+                "(the hosts source through jb_source_energy_sums / jb_source_photons_count_energy)");
   const DevMesh &M = mesh->dm;
   if (nranks > 1 && mesh->one_owner)
     return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: every block of the mesh view has the same owner -- a "

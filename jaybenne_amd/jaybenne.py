@@ -265,6 +265,9 @@ class MeshData:
         # radiation moments (EvaluateRadiationMoments; include/jaybenne_amd.h: jb_evaluate_radiation_moments): the
         # last call's device tensor (12, nblocks, nx3, nx2, nx1) and report; None until a host asks
         self.moments: Optional[torch.Tensor] = None
+        # source allocation (md.source_allocation; include/jaybenne_amd.h: jb_set_source_allocation): E_tot of the last
+        # source call under "energy"
+        self.source_e_total: Optional[float] = None
         self.moments_report: Optional[dict] = None
         # exact deposition (md.deposition; include/jaybenne_amd.h: jb_set_deposition): one record per cycle, the
         # counts of its close on this rank (jb_deposit_stats) and the cycle
@@ -469,6 +472,19 @@ class MeshData:
             _lib.check(self.lib.jb_source_tilt_slopes(self.pkg.ctx, self.handle, b, out[b].ctypes.data))
         return out.reshape((self.nowned, 3) + tuple(int(n) for n in m.nx[::-1]))
 
+    # ---- source allocation
+    @property
+    def source_allocation(self) -> str:
+        """``"uniform"`` (the default: every cell the same number of new photons, sourcing.cpp:68-69) or ``"energy"``:
+        ``SourcePhotons`` gives a cell photons in proportion to the energy it sources, ``num_particles`` over the whole
+        mesh per call, so that the new photons carry nearly equal weights (include/jaybenne_amd.h:
+        ``jb_set_source_allocation``)."""
+        return SOURCE_ALLOCATIONS[self.lib.jb_get_source_allocation(self.pkg.ctx)]
+
+    @source_allocation.setter
+    def source_allocation(self, mode: str) -> None:
+        _lib.check(self.lib.jb_set_source_allocation(self.pkg.ctx, source_allocation_code(mode)))
+
     def deposit_close(self) -> dict:
         """``jb_deposit_close`` on this rank's swarm, then the counts of that close (``jb_deposit_last``)."""
         self._sync_stream()
@@ -571,6 +587,33 @@ def _sum_over_ranks(md: MeshData, names) -> None:
             md.comm.allreduce_sum_tensor(md.fields[n])
 
 
+def gather_block_energies(md: MeshData, e_local: np.ndarray) -> np.ndarray:
+    """The block sums of the whole mesh by global block id from this rank's (``jb_source_energy_sums``: one per
+    resident block, 0 for a halo copy).  On a block partition they travel as bit patterns in a zero-filled int64
+    array through the integer all-reduce: each block has one owner, so the integer sum is an exact gather.  On a
+    replicated mesh every rank has summed every block itself."""
+    bits = np.zeros(md.mesh.nblocks, dtype=np.int64)
+    bits[md.gids] = np.ascontiguousarray(e_local[:md.nowned], dtype=np.float64).view(np.int64)
+    if md.comm is not None and md.nranks > 1 and not md.replicated:
+        bits = np.ascontiguousarray(md.comm.allreduce_sum_int64(bits), dtype=np.int64)
+    return bits.view(np.float64)
+
+
+def _count_by_energy(md: MeshData, source_type, dt: float, nper: np.ndarray) -> float:
+    """The count of a source call under ``source_allocation = energy``: energy pass, the total over the global block
+    ids in rising order (the library's host helper, so that every host adds alike), count pass.  Fills ``nper`` and
+    ``md.prefix``; returns ``E_tot``."""
+    pkg = md.pkg
+    e_local = np.zeros(md.nblocks, dtype=np.float64)
+    _lib.check(md.lib.jb_source_energy_sums(pkg.ctx, md.handle, int(source_type), dt, e_local.ctypes.data))
+    e_gid = np.ascontiguousarray(gather_block_energies(md, e_local), dtype=np.float64)
+    e_total = float(md.lib.jb_source_energy_total(e_gid.ctypes.data, int(md.mesh.nblocks)))
+    _lib.check(md.lib.jb_source_photons_count_energy(pkg.ctx, md.handle, int(source_type), dt,
+                                                     source_epoch(md.cycle, source_type), e_total,
+                                                     nper.ctypes.data, md.prefix.data_ptr()))
+    return e_total
+
+
 def source_epoch(cycle: int, source_type) -> int:
     """Key of the per-cell rounding streams of a source call (include/jaybenne_amd.hpp: SourceEpoch,
     shared by every host): 0 for the initial thermal source, k for the emission source of cycle k."""
@@ -592,9 +635,14 @@ def SourcePhotons(md: MeshData, source_type: SourceType, t_start: float, dt: flo
     md._sync_stream()
     nper = np.zeros(md.nblocks, dtype=np.int32)
     blocks_in_call = 1 if per_block else md.nowned   # vmesh.GetNBlocks() of this rank's MeshData
-    _lib.check(md.lib.jb_source_photons_count(pkg.ctx, md.handle, int(source_type), dt,
-                                              blocks_in_call, source_epoch(md.cycle, source_type),
-                                              nper.ctypes.data, md.prefix.data_ptr()))
+    if md.source_allocation == "energy":
+        # (num_particles over the whole mesh, dealt to the cells by the energy they source: the ranks' block sums are
+        # gathered between the energy pass and the count pass -- include/jaybenne_amd.h: jb_set_source_allocation)
+        md.source_e_total = _count_by_energy(md, source_type, dt, nper)
+    else:
+        _lib.check(md.lib.jb_source_photons_count(pkg.ctx, md.handle, int(source_type), dt,
+                                                  blocks_in_call, source_epoch(md.cycle, source_type),
+                                                  nper.ctypes.data, md.prefix.data_ptr()))
     if source_type == SourceType.emission and boundary_source_on(md):
         # the boundary photons of block b take the ids behind its emission photons: counted before the ids are dealt
         return _source_emission_and_count_boundary(md, nper, t_start, dt)
@@ -868,6 +916,21 @@ def DefragParticles(md: MeshData) -> TaskStatus:
 CELL_ORDERS = ("any", "id")
 DEPOSITIONS = ("atomic", "exact")
 SOURCE_TILTS = ("none", "linear")
+SOURCE_ALLOCATIONS = ("uniform", "energy")
+
+
+def source_allocation_code(mode: str, key: str = "source_allocation") -> int:
+    """``JB_ALLOC_UNIFORM`` / ``_ENERGY`` of ``uniform`` / ``energy`` (the values of the deck key
+    ``<jaybenne_amd> source_allocation``); anything else is an error that names ``key``."""
+    if mode not in SOURCE_ALLOCATIONS:
+        raise ValueError(f"{key} = {mode!r}: one of uniform, energy")
+    return SOURCE_ALLOCATIONS.index(mode)
+
+
+def SetSourceAllocation(md: "MeshData", mode: str) -> None:
+    """``md.source_allocation = mode``: ``"uniform"`` or ``"energy"`` (include/jaybenne_amd.h:
+    ``jb_set_source_allocation``)."""
+    md.source_allocation = mode
 
 
 def source_tilt_code(mode: str, key: str = "source_tilt") -> int:

@@ -278,6 +278,27 @@ def deck_source_tilt(pin: ParameterInput) -> str:
     return mode
 
 
+def deck_source_allocation(pin: ParameterInput) -> str:
+    """``<jaybenne_amd> source_allocation = uniform | energy``; without the key ``None`` (the library's default, which
+    JB_SOURCE_ALLOCATION sets); anything else raises with the key named.  (Not ``<jaybenne> source_strategy``, whose
+    value ``energy`` the reference rejects and so do we.)"""
+    mode = pin.GetOrAddString("jaybenne_amd", "source_allocation", "").strip()
+    if mode == "":
+        return None
+    if mode not in ("uniform", "energy"):
+        raise ValueError(f"jaybenne_amd/source_allocation = {mode!r}: one of uniform, energy")
+    return mode
+
+
+def source_allocation_of(pin: ParameterInput) -> str:
+    """The allocation a driver of this deck sources by: the deck key, else what JB_SOURCE_ALLOCATION makes the
+    library's default (``energy`` for exactly that value, as jb_initialize reads it), else ``uniform``."""
+    mode = deck_source_allocation(pin)
+    if mode is not None:
+        return mode
+    return "energy" if os.environ.get("JB_SOURCE_ALLOCATION") == "energy" else "uniform"
+
+
 # ------------------------------------------------------------------------------------------------
 # device-side driver (needs the HIP library; imported lazily so that the host-only helpers above
 # stay usable without a GPU)
@@ -323,8 +344,13 @@ class McblockDriver:
         if deposition == "exact" and replicated:
             raise ValueError("jaybenne_amd/deposition = exact: a replicated mesh sums its fields over the ranks in "
                              "floating point")
+        # (nor this one: photon numbers proportional to the energy a cell sources -- source_allocation = energy; read
+        # here because on a block partition the whole target can then fall to one rank's blocks)
+        allocation = source_allocation_of(pin)
         if replicated:
             share = self.pkg.Param("num_particles") / nranks
+        elif allocation == "energy":
+            share = self.pkg.Param("num_particles")
         else:
             n_local_blocks = int((self.mesh.owner == rank).sum()) if nranks > 1 else self.mesh.nblocks
             share = self.pkg.Param("num_particles") * n_local_blocks / self.mesh.nblocks
@@ -358,6 +384,9 @@ class McblockDriver:
         tilt = deck_source_tilt(pin)
         if tilt is not None and tilt != self.md.source_tilt:
             self.md.source_tilt = tilt
+        # (source_allocation, read above: set in front of InitializeRadiation, whose thermal source it covers too)
+        if allocation != self.md.source_allocation:
+            self.md.source_allocation = allocation
         # (nor these: the boundary source -- a black wall of temperature bsource_<face>_temperature behind a domain
         # face, bsource_num_particles photons per cycle over all such faces; every temperature 0 = off)
         self.md.bsource_num_particles = pin.GetOrAddInteger("jaybenne_amd", "bsource_num_particles", 0)
