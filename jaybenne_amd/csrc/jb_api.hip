@@ -54,6 +54,29 @@ static jb_status fail(jb_status st, const char *fmt, ...) {
                   __LINE__);                                                                 \
   } while (0)
 
+// A device buffer of the context's own that only grows; growing it does not keep its contents.
+struct DevBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+};
+static hipError_t dev_free(DevBuf &b) {
+  const hipError_t e = b.p ? hipFree(b.p) : hipSuccess;
+  b = DevBuf{};
+  return e;
+}
+// what: the message's subject ("<what> failed"); a failure leaves the buffer empty and no sticky error behind
+static jb_status dev_grow(DevBuf &b, size_t bytes, const char *what) {
+  if (bytes <= b.bytes) return JB_COMPLETE;
+  (void)dev_free(b);
+  if (hipMalloc(&b.p, bytes) != hipSuccess) {
+    b = DevBuf{};
+    (void)hipGetLastError();
+    return fail(JB_ERR_HIP, "%s failed", what);
+  }
+  b.bytes = bytes;
+  return JB_COMPLETE;
+}
+
 struct jb_context {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -65,8 +88,7 @@ struct jb_context {
   int num_cu = 256;
   unsigned long long *counters_d = nullptr;   // CNT_N + 2 cursors + per-rank counters
   unsigned long long *counters_h = nullptr;   // pinned
-  unsigned long long *xch_d = nullptr;        // jb_exchange: the gathered count matrix + pack offsets
-  int xch_ranks = 0;                          // ... sized for this many ranks
+  DevBuf xch;                                 // jb_exchange: the gathered count matrix + pack offsets (u64)
   long long *scratch_d = nullptr;             // holes / movers / small tables
   bool scratch_alloc_failed = false;          // set by ensure_scratch when hipMalloc itself said no
   std::vector<unsigned long long> xch_matrix;  // jb_exchange: the rank x rank record counts (host copy)
@@ -88,14 +110,10 @@ struct jb_context {
   } comb;
   // jb_radiation_step_ranks: the hand-off record buffers (JB_RECORD_WORDS words per record) and the buffer of
   // the step's first all-gather ([status | counts per global block] of this rank, then every rank's)
-  long long *step_send_d = nullptr, *step_recv_d = nullptr;
-  long long step_send_cap = 0, step_recv_cap = 0;
-  unsigned long long *step_gather_d = nullptr;
-  size_t step_gather_words = 0;
+  DevBuf step_send, step_recv, step_gather;
   long long min_records = 0;  // JB_HANDOFF_MIN_RECORDS at jb_initialize: first size of those record buffers (tests)
   // jb_evaluate_radiation_moments_host: the device array the fields pass through
-  double *moments_d = nullptr;
-  size_t moments_words = 0;
+  DevBuf moments;
   // arithmetic of the gray IMC tracking step: lean (default) or exact (JB_EXACT_ARITH=1 in the
   // environment at jb_initialize, or jb_set_arithmetic)
   bool lean_arith = true;
@@ -129,17 +147,14 @@ struct jb_context {
   bool ledger_on = false;
   unsigned long long *ledger_d = nullptr;    // [kLedgerHead words: the running ledger | the workgroups' partial sums]
   int ledger_parts = 0;                      // workgroups the partials have room for
-  unsigned long long *ledger_gather_d = nullptr;   // jb_ledger_reduce: this rank's ledger, then every rank's
-  size_t ledger_gather_words = 0;
+  DevBuf ledger_gather;                      // jb_ledger_reduce: this rank's ledger, then every rank's (u64)
   jb_energy_ledger ledger_last{};
   bool ledger_has_last = false;
   // boundary source (jb_set_boundary_source; jb_kernel_bsource.hpp): off (every temperature 0) by default
   double bs_temp[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   long long bs_num_particles = 0, bs_face_cells_total = 0;   // what the step calls ask for (jb_set_boundary_source_count)
-  int *bs_prefix_d = nullptr;          // the step calls' prefix workspace (a host that drives the tasks brings its own)
-  size_t bs_prefix_words = 0;
-  char *bs_out_d = nullptr;            // [nblocks] counts, [nblocks][6] photons and energy of the last count call
-  size_t bs_out_blocks = 0;
+  DevBuf bs_prefix;                    // the step calls' prefix workspace (a host that drives the tasks brings its own)
+  DevBuf bs_out;                       // [nblocks] counts, [nblocks][6] photons and energy of the last count call
   jb_boundary_source_record bs_last{};
   // exact deposition (jb_set_deposition; JB_DEPOSITION=exact at jb_initialize; jb_kernel_deposit.hpp): off by default
   int deposition = JB_DEPOSIT_ATOMIC;
@@ -599,15 +614,10 @@ extern "C" jb_status jb_finalize(jb_context *ctx) {
   if (ctx->counters_d) (void)hipFree(ctx->counters_d);
   if (ctx->counters_h) (void)hipHostFree(ctx->counters_h);
   if (ctx->scratch_d) (void)hipFree(ctx->scratch_d);
-  if (ctx->xch_d) (void)hipFree(ctx->xch_d);
-  if (ctx->step_send_d) (void)hipFree(ctx->step_send_d);
-  if (ctx->step_recv_d) (void)hipFree(ctx->step_recv_d);
-  if (ctx->step_gather_d) (void)hipFree(ctx->step_gather_d);
   if (ctx->ledger_d) (void)hipFree(ctx->ledger_d);
-  if (ctx->ledger_gather_d) (void)hipFree(ctx->ledger_gather_d);
-  if (ctx->bs_prefix_d) (void)hipFree(ctx->bs_prefix_d);
-  if (ctx->bs_out_d) (void)hipFree(ctx->bs_out_d);
-  if (ctx->moments_d) (void)hipFree(ctx->moments_d);
+  for (DevBuf *b : {&ctx->xch, &ctx->step_send, &ctx->step_recv, &ctx->step_gather, &ctx->moments, &ctx->ledger_gather,
+                    &ctx->bs_prefix, &ctx->bs_out})
+    (void)dev_free(*b);
   for (hipEvent_t e : ctx->tev) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->sort_ev) if (e) (void)hipEventDestroy(e);
   delete ctx;
@@ -1381,18 +1391,6 @@ extern "C" jb_status jb_boundary_source_last(const jb_context *ctx, jb_boundary_
   return JB_COMPLETE;
 }
 
-// the library's own prefix workspace (prefix_dev == NULL; the step calls)
-static jb_status bsource_step_prefix(jb_context *ctx, const jb_mesh *mesh) {
-  const size_t words = (size_t)jb_boundary_prefix_words(mesh);
-  if (ctx->bs_prefix_words >= words) return JB_COMPLETE;
-  if (ctx->bs_prefix_d) (void)hipFree(ctx->bs_prefix_d);
-  ctx->bs_prefix_d = nullptr;
-  ctx->bs_prefix_words = 0;
-  JB_HIP(hipMalloc(&ctx->bs_prefix_d, words * sizeof(int)));
-  ctx->bs_prefix_words = words;
-  return JB_COMPLETE;
-}
-
 // the (block, face) results of the count kernel: [nblocks] int | pad to 8 | [nblocks][6] long long | [nblocks][6] double
 static size_t bsource_out_counts(size_t nblocks) { return (nblocks * sizeof(int) + 7) / 8 * 8; }
 
@@ -1416,9 +1414,10 @@ extern "C" jb_status jb_source_boundary_count(jb_context *ctx, jb_mesh *mesh, do
       return fail(JB_ERR_INVALID, "boundary source on face %d: its swarm boundary is periodic", f);
   }
   if (!prefix_dev) {   // the library's own workspace
-    const jb_status pst = bsource_step_prefix(ctx, mesh);
+    const jb_status pst = dev_grow(ctx->bs_prefix, (size_t)jb_boundary_prefix_words(mesh) * sizeof(int),
+                                   "hipMalloc of the boundary source's prefix workspace");
     if (pst != JB_COMPLETE) return pst;
-    prefix_dev = ctx->bs_prefix_d;
+    prefix_dev = (int32_t *)ctx->bs_prefix.p;
   }
   if (epoch >= (1u << 20))  // cell_stream_id keeps the source-call counter in 20 bits
     return fail(JB_ERR_INVALID, "more than 2^20 source calls: the per-cell rounding streams would repeat");
@@ -1429,15 +1428,10 @@ extern "C" jb_status jb_source_boundary_count(jb_context *ctx, jb_mesh *mesh, do
                 (long long)num_particles, (long long)face_cells_total);
   if (!(npc < 2.0e9)) return fail(JB_ERR_INVALID, "boundary source: more than 2e9 photons per source face cell");
   const size_t nb = (size_t)M.nblocks;
-  if (ctx->bs_out_blocks < nb) {
-    if (ctx->bs_out_d) (void)hipFree(ctx->bs_out_d);
-    ctx->bs_out_d = nullptr;
-    ctx->bs_out_blocks = 0;
-    JB_HIP(hipMalloc(&ctx->bs_out_d, bsource_out_counts(nb) + nb * 6 * 16));
-    ctx->bs_out_blocks = nb;
-  }
-  int *nper_d = (int *)ctx->bs_out_d;
-  long long *n_bf_d = (long long *)(ctx->bs_out_d + bsource_out_counts(nb));
+  const jb_status ost = dev_grow(ctx->bs_out, bsource_out_counts(nb) + nb * 6 * 16, "hipMalloc of the boundary source's counts");
+  if (ost != JB_COMPLETE) return ost;
+  int *nper_d = (int *)ctx->bs_out.p;
+  long long *n_bf_d = (long long *)((char *)ctx->bs_out.p + bsource_out_counts(nb));
   double *e_bf_d = (double *)(n_bf_d + 6 * nb);
   BsFaces F;
   for (int f = 0; f < 6; ++f) F.temp[f] = ctx->bs_temp[f];
@@ -1447,7 +1441,7 @@ extern "C" jb_status jb_source_boundary_count(jb_context *ctx, jb_mesh *mesh, do
   JB_HIP(hipGetLastError());
   ctx->bs_last.kernel_launches += 1;
   std::vector<char> host(bsource_out_counts(nb) + nb * 6 * 16);
-  JB_HIP(hipMemcpyAsync(host.data(), ctx->bs_out_d, host.size(), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipMemcpyAsync(host.data(), ctx->bs_out.p, host.size(), hipMemcpyDeviceToHost, ctx->stream));
   JB_HIP(hipStreamSynchronize(ctx->stream));
   const int *nper_h = (const int *)host.data();
   const long long *n_bf = (const long long *)(host.data() + bsource_out_counts(nb));
@@ -1474,7 +1468,7 @@ extern "C" jb_status jb_source_boundary_fill(jb_context *ctx, jb_mesh *mesh, con
   jb_status st = check_swarm(swarm, "jb_source_boundary_fill");
   if (st != JB_COMPLETE) return st;
   if (!bsource_on(ctx)) return JB_COMPLETE;
-  if (!prefix_dev) prefix_dev = ctx->bs_prefix_d;   // the library's own workspace, as the count call filled it
+  if (!prefix_dev) prefix_dev = (int32_t *)ctx->bs_prefix.p;   // the library's own workspace, as the count call filled it
   if (!prefix_dev) return fail(JB_ERR_INVALID, "jb_source_boundary_fill: no count call has filled the prefix workspace");
   const DevMesh &M = mesh->dm;
   st = ensure_scratch(ctx, (size_t)M.nblocks * 3 + 8);
@@ -2061,30 +2055,59 @@ extern "C" jb_status jb_remove_marked_particles(jb_context *ctx, jb_swarm_view *
   return JB_COMPLETE;
 }
 
-// scratch of the sort, in 8-byte words: the particle records (16 words each, on a 128-byte boundary), then
-// histogram / offsets (nbins), tile sums (ntiles) and keys (n), 4 bytes each; under JB_CELL_ORDER_BY_ID the arrays
-// of the canonical sort behind them (jb_order_plan.hpp: order_layout)
-static size_t sort_scratch_words(const jb_context *ctx, long long n, long long nbins, int ntiles) {
-  const size_t words = (size_t)kSortRecWords * (size_t)n + (size_t)((nbins + ntiles + n) / 2 + 16);
-  return ctx->cell_order == JB_CELL_ORDER_BY_ID ? order_layout(n, words).end : words;
+// The scratch of the sort, the comb and the moments: jb_scratch_layout.hpp says where the arrays lie, and these
+// turn a layout into pointers.
+template <class T>
+static T *scratch_at(const jb_context *ctx, const Span &a) { return (T *)((char *)ctx->scratch_d + a.off); }
+struct SortScratch {
+  unsigned long long *rec;
+  unsigned *hist, *sums, *key;   // hist: the histogram, then the cells' starts (its scan) or ends (behind a move)
+};
+static SortScratch sort_scratch(const jb_context *ctx, const SortLayout &L) {
+  return {scratch_at<unsigned long long>(ctx, L.rec), scratch_at<unsigned>(ctx, L.hist), scratch_at<unsigned>(ctx, L.sums),
+          scratch_at<unsigned>(ctx, L.key)};
 }
-static OrderLayout sort_order_layout(long long n, long long nbins, int ntiles) {
-  return order_layout(n, (size_t)kSortRecWords * (size_t)n + (size_t)((nbins + ntiles + n) / 2 + 16));
+static bool order_by_id(const jb_context *ctx) { return ctx->cell_order == JB_CELL_ORDER_BY_ID; }
+// the limits of the 32-bit keys and slot indices, in the words of the entry point `who`
+static jb_status check_cell_keys(const CellKeys &k, const char *who) {
+  if (k.over == KEYS_PARTICLES) return fail(JB_ERR_INVALID, "%s: more than 2^32 - 1 particles", who);
+  if (k.over == KEYS_CELLS) return fail(JB_ERR_INVALID, "%s: more than 2^32 - 2 cells", who);
+  return JB_COMPLETE;
+}
+// in-place exclusive scan of the n words of `data`; sums: a word per tile of kScanTile
+static void scan_u32(jb_context *ctx, unsigned *data, long long n, unsigned *sums) {
+  const int tiles = (int)((n + kScanTile - 1) / kScanTile);
+  hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(kBlock), 0, ctx->stream, data, n, sums);
+  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums, tiles);
+  hipLaunchKernelGGL(k_scan_add, dim3(tiles), dim3(kBlock), 0, ctx->stream, data, n, (const unsigned *)sums);
+}
+// the keys of the first n slots and their histogram (scan_u32 makes the cells' starts of it)
+static jb_status count_cells(jb_context *ctx, const DevMesh &M, const DevSwarm &S, long long n, const CellKeys &k,
+                             const SortScratch &p) {
+  JB_HIP(hipMemsetAsync(p.hist, 0, sizeof(unsigned) * (size_t)k.nbins, ctx->stream));
+  hipLaunchKernelGGL(k_sort_count, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream, M, S, n, k.nkeys, p.key, p.hist);
+  return JB_COMPLETE;
+}
+// the schedule of jb_defrag_policy starts over from a sorted swarm
+static void defrag_schedule_restart(jb_context *ctx) {
+  ctx->rate_ref = 0.0;
+  ctx->rate_before_sort = 0.0;
+  ctx->excess_ms = 0.0;
+  ctx->cycles_since_sort = 0;
 }
 
 // The canonical sort (jb_kernel_order.hpp): the first n slots by (sort key, id, input slot).  key: n words of
 // scratch for the sort keys (written here).  *moved = 0: the swarm was in that order already and nothing was
 // touched.  Synchronises the stream once, for the read-back of k_order_check.
-static jb_status order_sort(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, long long nbins, int ntiles,
-                            int *moved) {
+static jb_status order_sort(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, unsigned nkeys,
+                            const SortLayout &sort, int *moved) {
   *moved = 0;
   const long long n = swarm->n;
   const DevMesh &M = mesh->dm;
-  const unsigned nkeys = (unsigned)(nbins - 1);
-  const OrderLayout L = sort_order_layout(n, nbins, ntiles);
+  const OrderLayout &L = sort.order;
   unsigned long long *base = (unsigned long long *)ctx->scratch_d;
-  unsigned long long *rec = base;
-  unsigned *key = (unsigned *)(base + (size_t)kSortRecWords * (size_t)n) + nbins + ntiles;
+  unsigned long long *rec = scratch_at<unsigned long long>(ctx, sort.rec);
+  unsigned *key = scratch_at<unsigned>(ctx, sort.key);
   unsigned long long *pairs[2] = {base + L.pairs[0], base + L.pairs[1]};
   unsigned *dest = (unsigned *)(base + L.dest), *cnt = (unsigned *)(base + L.cnt), *csum = (unsigned *)(base + L.csum);
   OrderFlags *flags_d = (OrderFlags *)(base + L.flags);
@@ -2099,16 +2122,14 @@ static jb_status order_sort(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view 
   JB_HIP(hipStreamSynchronize(ctx->stream));
   const OrderPlan plan = plan_order(n, flags.max_id, flags.max_key);
   if (!flags.unsorted || plan.npasses == 0) return JB_COMPLETE;
-  const int tiles = (int)L.tiles, scan_tiles = (int)L.scan_tiles;
+  const int tiles = (int)L.tiles;
   hipLaunchKernelGGL(k_order_init, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)key, (const uint64_t *)S.id, n,
                      plan.pass[0].word, pairs[0]);
   for (int q = 0; q < plan.npasses; ++q) {
     const OrderPass &ps = plan.pass[q];
     const unsigned long long *in = pairs[q & 1];
     hipLaunchKernelGGL(k_order_count, dim3(tiles), dim3(kBlock), 0, ctx->stream, in, n, ps.shift, cnt, L.tiles);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(scan_tiles), dim3(kBlock), 0, ctx->stream, cnt, L.ncnt, csum);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, csum, scan_tiles);
-    hipLaunchKernelGGL(k_scan_add, dim3(scan_tiles), dim3(kBlock), 0, ctx->stream, cnt, L.ncnt, (const unsigned *)csum);
+    scan_u32(ctx, cnt, L.ncnt, csum);
     hipLaunchKernelGGL(k_order_scatter, dim3(tiles), dim3(kBlock), 0, ctx->stream, in, n, ps.shift, (const unsigned *)cnt,
                        L.tiles, ps.next, (const unsigned *)key, (const uint64_t *)S.id, pairs[(q + 1) & 1], dest);
   }
@@ -2127,79 +2148,48 @@ extern "C" jb_status jb_defrag_particles(jb_context *ctx, jb_mesh *mesh, const j
   if (st != JB_COMPLETE) return st;
   const long long n = swarm->n;
   if (n == 0) return JB_COMPLETE;
-  if (n >= (1ll << 32)) return fail(JB_ERR_INVALID, "jb_defrag_particles: more than 2^32 - 1 particles");
   const DevMesh &M = mesh->dm;
-  const unsigned long long nkeys64 = (unsigned long long)M.nblocks * (unsigned long long)M.ntot;
-  if (nkeys64 >= (1ull << 32) - 1ull) return fail(JB_ERR_INVALID, "jb_defrag_particles: more than 2^32 - 2 cells");
-  const unsigned nkeys = (unsigned)nkeys64;
-  const long long nbins = (long long)nkeys + 1;                       // + the bin behind all cells
-  const int ntiles = (int)((nbins + kScanTile - 1) / kScanTile);
-  const size_t rec_words = (size_t)kSortRecWords * (size_t)n;
-  st = ensure_scratch(ctx, sort_scratch_words(ctx, n, nbins, ntiles), /*slack=*/false);
+  const CellKeys k = cell_keys(M.nblocks, M.ntot, n);
+  if ((st = check_cell_keys(k, "jb_defrag_particles")) != JB_COMPLETE) return st;
+  const SortLayout L = sort_layout(n, k.nbins, order_by_id(ctx));
+  st = ensure_scratch(ctx, L.words, /*slack=*/false);
   if (st != JB_COMPLETE) return st;
-  if (ctx->cell_order == JB_CELL_ORDER_BY_ID) {
+  if (L.by_id) {
     int moved = 0;
-    return order_sort(ctx, mesh, swarm, nbins, ntiles, &moved);
+    return order_sort(ctx, mesh, swarm, k.nkeys, L, &moved);
   }
-  unsigned long long *rec = (unsigned long long *)ctx->scratch_d;
-  unsigned *hist = (unsigned *)(rec + rec_words);
-  unsigned *sums = hist + nbins;
-  unsigned *key = sums + ntiles;
-  JB_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned) * (size_t)nbins, ctx->stream));
+  const SortScratch p = sort_scratch(ctx, L);
   const DevSwarm S = dev_swarm(swarm);
-  hipLaunchKernelGGL(k_sort_count, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, key, hist);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kBlock), 0, ctx->stream, hist, nbins, sums);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums, ntiles);
-  hipLaunchKernelGGL(k_scan_add, dim3(ntiles), dim3(kBlock), 0, ctx->stream, hist, nbins, (const unsigned *)sums);
-  hipLaunchKernelGGL(k_sort_pack, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream, S, n, (const unsigned *)key,
-                     hist, rec);
+  if ((st = count_cells(ctx, M, S, n, k, p)) != JB_COMPLETE) return st;
+  scan_u32(ctx, p.hist, k.nbins, p.sums);
+  hipLaunchKernelGGL(k_sort_pack, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream, S, n, (const unsigned *)p.key,
+                     p.hist, p.rec);
   hipLaunchKernelGGL(k_sort_unpack, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream, S, n,
-                     (const unsigned long long *)rec);
+                     (const unsigned long long *)p.rec);
   JB_HIP(hipGetLastError());
   return JB_COMPLETE;
 }
 
 // ------------------------------------------------------------------------------------------------
-// Census comb (jb_kernel_comb.hpp).  Scratch behind the sort's: C (n doubles), kcnt / extra (n + 1 words of 4
-// bytes each; the scans turn them into output slots and id offsets), the scans' tile sums, the partial sums.
-constexpr int kCombParts = 1024;   // workgroups of k_comb_cells / k_comb_energy at the most
-struct CombScratch {
-  unsigned long long *rec;
-  unsigned *ends, *key, *kcnt, *extra, *ssum, *tflag;
+// Census comb (jb_kernel_comb.hpp).  Its scratch lies behind the sort's (jb_scratch_layout.hpp: comb_layout).
+struct CombScratch : SortScratch {
+  unsigned *kcnt, *extra, *ssum, *tflag;
   double *C, *tsum, *epart;
   unsigned long long *cpart;
-  int ntiles;      // tiles of kScanTile over the n + 1 slots
-  size_t words;
+  U128 *C128, *tsum128;   // (canonical order: in the records' memory)
 };
-static CombScratch comb_scratch(const jb_context *ctx, long long n, long long nbins) {
-  CombScratch c{};
-  const int sort_tiles = (int)((nbins + kScanTile - 1) / kScanTile);
-  c.ntiles = (int)((n + 1 + kScanTile - 1) / kScanTile);
-  const size_t nt = (size_t)c.ntiles, half = (size_t)(n + 2) / 2;
-  // offsets in 8-byte words from the start of the scratch memory (the sort's part: the layout of jb_defrag_particles)
-  size_t o = sort_scratch_words(ctx, n, nbins, sort_tiles);
-  const size_t oC = o; o += (size_t)n;
-  const size_t okcnt = o; o += half;
-  const size_t oextra = o; o += half;
-  const size_t ossum = o; o += (nt + 1) / 2;
-  const size_t otsum = o; o += nt;
-  const size_t otflag = o; o += (nt + 1) / 2;
-  const size_t ocpart = o; o += 2 * kCombParts;
-  const size_t oepart = o; o += kCombParts;
-  c.words = o;
-  unsigned long long *base = (unsigned long long *)ctx->scratch_d;
-  if (!base) return c;   // (asked for the size alone)
-  c.rec = base;
-  c.ends = (unsigned *)(base + (size_t)kSortRecWords * (size_t)n);
-  c.key = c.ends + nbins + sort_tiles;
-  c.C = (double *)(base + oC);
-  c.kcnt = (unsigned *)(base + okcnt);
-  c.extra = (unsigned *)(base + oextra);
-  c.ssum = (unsigned *)(base + ossum);
-  c.tsum = (double *)(base + otsum);
-  c.tflag = (unsigned *)(base + otflag);
-  c.cpart = base + ocpart;
-  c.epart = (double *)(base + oepart);
+static CombScratch comb_scratch(const jb_context *ctx, const CombLayout &L) {
+  CombScratch c{sort_scratch(ctx, L.sort)};
+  c.kcnt = scratch_at<unsigned>(ctx, L.kcnt);
+  c.extra = scratch_at<unsigned>(ctx, L.extra);
+  c.ssum = scratch_at<unsigned>(ctx, L.ssum);
+  c.tflag = scratch_at<unsigned>(ctx, L.tflag);
+  c.C = scratch_at<double>(ctx, L.C);
+  c.tsum = scratch_at<double>(ctx, L.tsum);
+  c.epart = scratch_at<double>(ctx, L.epart);
+  c.cpart = scratch_at<unsigned long long>(ctx, L.cpart);
+  c.C128 = scratch_at<U128>(ctx, L.C128);
+  c.tsum128 = scratch_at<U128>(ctx, L.tsum128);
   return c;
 }
 static int comb_parts(long long n) {
@@ -2239,29 +2229,28 @@ extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swar
   const long long n = swarm->n;
   out->n_before = out->n_after = n;
   if (n == 0) return JB_COMPLETE;
-  if (n >= (1ll << 32)) return fail(JB_ERR_INVALID, "jb_comb_census_plan: more than 2^32 - 1 particles");
   const DevMesh &M = mesh->dm;
-  const unsigned long long nkeys64 = (unsigned long long)M.nblocks * (unsigned long long)M.ntot;
-  if (nkeys64 >= (1ull << 32) - 1ull) return fail(JB_ERR_INVALID, "jb_comb_census_plan: more than 2^32 - 2 cells");
-  const unsigned nkeys = (unsigned)nkeys64;
-  const long long nbins = (long long)nkeys + 1;
+  const CellKeys k = cell_keys(M.nblocks, M.ntot, n);
+  if ((st = check_cell_keys(k, "jb_comb_census_plan")) != JB_COMPLETE) return st;
+  const unsigned nkeys = k.nkeys;
+  const bool by_id = order_by_id(ctx);
+  const CombLayout L = comb_layout(n, k.nbins, by_id);
   // (all of the scratch first: the sort then finds room, and a failed allocation leaves the swarm as it was)
-  st = ensure_scratch(ctx, comb_scratch(ctx, n, nbins).words, /*slack=*/false);
+  st = ensure_scratch(ctx, L.words, /*slack=*/false);
   if (st != JB_COMPLETE) return st;
-  const CombScratch c = comb_scratch(ctx, n, nbins);
+  const CombScratch c = comb_scratch(ctx, L);
   const DevSwarm S = dev_swarm(swarm);
   const unsigned T = (unsigned)trigger_T, K = (unsigned)target_K;
-  const int gn = grid_for(ctx, n), gc = comb_parts((long long)nkeys), nt = c.ntiles;
+  const int gn = grid_for(ctx, n), gc = comb_parts((long long)nkeys), nt = L.ntiles;
   // In key order already (behind a DefragParticles, or a comb, that nothing has moved since)?  Then the sort's
   // move is left out -- and the order within a cell, which the move leaves to its atomics, stays the caller's:
   // the same sorted swarm then gives the same bits.
   // Under JB_CELL_ORDER_BY_ID the test is "in canonical order already?", the sort is the canonical one (which makes
   // that test itself), and the cells' ends come from the histogram and its scan either way.
-  const bool by_id = ctx->cell_order == JB_CELL_ORDER_BY_ID;
   unsigned unsorted = 0u;
   if (by_id) {
     int moved = 0;
-    st = order_sort(ctx, mesh, swarm, nbins, (int)((nbins + kScanTile - 1) / kScanTile), &moved);
+    st = order_sort(ctx, mesh, swarm, nkeys, L.sort, &moved);
     if (st != JB_COMPLETE) return st;
     unsorted = moved ? 1u : 0u;
   } else {
@@ -2273,35 +2262,26 @@ extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swar
     JB_HIP(hipMemcpyAsync(&unsorted, flag_d, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     JB_HIP(hipStreamSynchronize(ctx->stream));
   }
-  const unsigned *ends = c.ends;
+  const unsigned *ends = c.hist;   // (behind the move of jb_defrag_particles: the cells' ends)
   if (unsorted) {
     if (!by_id) {
       st = jb_defrag_particles(ctx, mesh, swarm);
       if (st != JB_COMPLETE) return st;
     }
-    // the schedule of jb_defrag_policy starts over from a sorted swarm (as behind defrag_now; this sort is not
-    // the one whose time the policy weighs against the kernels' loss)
-    ctx->rate_ref = 0.0;
-    ctx->rate_before_sort = 0.0;
-    ctx->excess_ms = 0.0;
-    ctx->cycles_since_sort = 0;
+    // (as behind defrag_now; this sort is not the one whose time the policy weighs against the kernels' loss)
+    defrag_schedule_restart(ctx);
     out->sorted = 1;
     if (!by_id) hipLaunchKernelGGL(k_comb_keys, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, c.key);
   }
   if (by_id || !unsorted) {   // the histogram and its scan alone: the cells' starts, the ends one entry on
-    const int sort_tiles = (int)((nbins + kScanTile - 1) / kScanTile);
-    unsigned *hist = c.ends, *sums = hist + nbins;
-    JB_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned) * (size_t)nbins, ctx->stream));
-    hipLaunchKernelGGL(k_sort_count, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, c.key, hist);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(sort_tiles), dim3(kBlock), 0, ctx->stream, hist, nbins, sums);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums, sort_tiles);
-    hipLaunchKernelGGL(k_scan_add, dim3(sort_tiles), dim3(kBlock), 0, ctx->stream, hist, nbins, (const unsigned *)sums);
-    ends = hist + 1;
+    if ((st = count_cells(ctx, M, S, n, k, c)) != JB_COMPLETE) return st;
+    scan_u32(ctx, c.hist, k.nbins, c.sums);
+    ends = c.hist + 1;
   }
   if (by_id) {
     // exact running weights (jb_kernel_comb.hpp): 128-bit sums in the records' memory, which nothing uses before
-    // the move (2 n words, then 2 per tile: nt <= 7 n); the cells' scales where k_comb_decide's counts go later
-    U128 *C128 = (U128 *)c.rec, *tsum128 = C128 + n;
+    // the move (CombLayout::fits_records); the cells' scales where k_comb_decide's counts go later
+    U128 *C128 = c.C128, *tsum128 = c.tsum128;
     unsigned *cexp = c.kcnt;
     JB_HIP(hipMemsetAsync(cexp, 0, sizeof(unsigned) * (size_t)(n + 1), ctx->stream));
     hipLaunchKernelGGL(k_comb_cell_exp, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key,
@@ -2322,11 +2302,7 @@ extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swar
                      (const unsigned *)c.key, ends, (const double *)c.C, T, K, ctx->dp.key0, epoch,
                      c.kcnt, c.extra);
   hipLaunchKernelGGL(k_comb_cells, dim3(gc), dim3(kBlock), 0, ctx->stream, nkeys, ends, (const double *)c.C, T, c.cpart);
-  for (unsigned *data : {c.kcnt, c.extra}) {
-    hipLaunchKernelGGL(k_scan_tiles, dim3(nt), dim3(kBlock), 0, ctx->stream, data, n + 1, c.ssum);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, c.ssum, nt);
-    hipLaunchKernelGGL(k_scan_add, dim3(nt), dim3(kBlock), 0, ctx->stream, data, n + 1, (const unsigned *)c.ssum);
-  }
+  for (unsigned *data : {c.kcnt, c.extra}) scan_u32(ctx, data, n + 1, c.ssum);
   JB_HIP(hipGetLastError());
   unsigned totals[2] = {0u, 0u};
   std::vector<unsigned long long> cpart((size_t)(2 * gc));
@@ -2370,11 +2346,12 @@ extern "C" jb_status jb_comb_census_apply(jb_context *ctx, jb_mesh *mesh, jb_swa
   ctx->comb.valid = false;
   const long long n = ctx->comb.n, n_after = ctx->comb.n_after;
   const DevMesh &M = mesh->dm;
-  const unsigned nkeys = (unsigned)((unsigned long long)M.nblocks * (unsigned long long)M.ntot);
-  const CombScratch c = comb_scratch(ctx, n, (long long)nkeys + 1);
+  const CellKeys k = cell_keys(M.nblocks, M.ntot, n);   // (within the limits: the plan was made)
+  const unsigned nkeys = k.nkeys;
+  const CombScratch c = comb_scratch(ctx, comb_layout(n, k.nbins, order_by_id(ctx)));
   const DevSwarm S = dev_swarm(swarm);
   hipLaunchKernelGGL(k_comb_pack, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream, S, n, nkeys,
-                     (const unsigned *)c.key, (const unsigned *)c.ends + ctx->comb.ends_shift, (const double *)c.C,
+                     (const unsigned *)c.key, (const unsigned *)c.hist + ctx->comb.ends_shift, (const double *)c.C,
                      (const unsigned *)c.kcnt,
                      (const unsigned *)c.extra, ctx->comb.T, ctx->comb.K, ctx->dp.key0, (unsigned long long)id_base, c.rec);
   if (n_after > 0)
@@ -2388,32 +2365,16 @@ extern "C" jb_status jb_comb_census_apply(jb_context *ctx, jb_mesh *mesh, jb_swa
 }
 
 // ------------------------------------------------------------------------------------------------
-// Radiation moments (jb_kernel_moments.hpp).  Scratch behind the sort's: the chunks' partial sums (two places of
-// kMomSums doubles per kMomChunk slots), the three counts of the report, the "out of order" flag.
+// Radiation moments (jb_kernel_moments.hpp).  Their scratch lies behind the sort's (jb_scratch_layout.hpp: mom_layout).
 static_assert(kMoments == JB_MOMENTS && sizeof(jb_moments_report) == 40, "jb_limits.hpp restates the header");
-struct MomScratch {
-  unsigned *start, *key, *flag;
+struct MomScratch : SortScratch {
   double *part;
   unsigned long long *stats;
-  int sort_tiles;
-  size_t words;
+  unsigned *flag;
 };
-static MomScratch mom_scratch(const jb_context *ctx, long long n, long long nbins) {
-  MomScratch m{};
-  m.sort_tiles = (int)((nbins + kScanTile - 1) / kScanTile);
-  size_t o = sort_scratch_words(ctx, n, nbins, m.sort_tiles);
-  const size_t opart = o; o += (size_t)kMomSums * 2 * (size_t)((n + kMomChunk - 1) / kMomChunk);
-  const size_t ostats = o; o += MS_N;
-  const size_t oflag = o; o += 1;
-  m.words = o;
-  unsigned long long *base = (unsigned long long *)ctx->scratch_d;
-  if (!base) return m;   // (asked for the size alone)
-  m.start = (unsigned *)(base + (size_t)kSortRecWords * (size_t)n);
-  m.key = m.start + nbins + m.sort_tiles;
-  m.part = (double *)(base + opart);
-  m.stats = base + ostats;
-  m.flag = (unsigned *)(base + oflag);
-  return m;
+static MomScratch mom_scratch(const jb_context *ctx, const MomLayout &L) {
+  return {sort_scratch(ctx, L.sort), scratch_at<double>(ctx, L.part), scratch_at<unsigned long long>(ctx, L.stats),
+          scratch_at<unsigned>(ctx, L.flag)};
 }
 // lanes per cell of k_mom_cells: the power of two that holds about twice the mean run and two more
 static int mom_group(long long n, long long cells) {
@@ -2439,35 +2400,33 @@ extern "C" jb_status jb_evaluate_radiation_moments(jb_context *ctx, jb_mesh *mes
   jb_status st = check_swarm(swarm, "jb_evaluate_radiation_moments");
   if (st != JB_COMPLETE) return st;
   const long long n = swarm->n;
-  if (n >= (1ll << 32)) return fail(JB_ERR_INVALID, "jb_evaluate_radiation_moments: more than 2^32 - 1 particles");
   const DevMesh &M = mesh->dm;
-  const unsigned long long nkeys64 = (unsigned long long)M.nblocks * (unsigned long long)M.ntot;
-  if (nkeys64 >= (1ull << 32) - 1ull) return fail(JB_ERR_INVALID, "jb_evaluate_radiation_moments: more than 2^32 - 2 cells");
-  const unsigned nkeys = (unsigned)nkeys64;
-  const long long nbins = (long long)nkeys + 1;
+  const CellKeys k = cell_keys(M.nblocks, M.ntot, n);
+  if ((st = check_cell_keys(k, "jb_evaluate_radiation_moments")) != JB_COMPLETE) return st;
+  const unsigned nkeys = k.nkeys;
   const long long cells = (long long)M.nblocks * M.ncell;
   if (report) memset(report, 0, sizeof *report);
+  const bool by_id = order_by_id(ctx);
+  const MomLayout L = mom_layout(n, k.nbins, by_id);
   // (all of the scratch first: the sort then finds room, and a failed allocation leaves the swarm as it was)
-  st = ensure_scratch(ctx, mom_scratch(ctx, n, nbins).words, /*slack=*/false);
+  st = ensure_scratch(ctx, L.words, /*slack=*/false);
   if (st != JB_COMPLETE) return st;
   ctx->comb.valid = false;   // (a comb plan not yet applied lived in this memory)
-  const MomScratch m = mom_scratch(ctx, n, nbins);
+  const MomScratch m = mom_scratch(ctx, L);
   const DevSwarm S = dev_swarm(swarm);
   const int gn = grid_for(ctx, n);
   // In order already?  As jb_comb_census_plan asks: key order under JB_CELL_ORDER_ANY, the canonical order -- whose
   // sort makes that test itself -- under JB_CELL_ORDER_BY_ID.
-  const bool by_id = ctx->cell_order == JB_CELL_ORDER_BY_ID;
   unsigned unsorted = 0u;
   if (n > 0 && by_id) {
     int moved = 0;
-    st = order_sort(ctx, mesh, swarm, nbins, m.sort_tiles, &moved);
+    st = order_sort(ctx, mesh, swarm, nkeys, L.sort, &moved);
     if (st != JB_COMPLETE) return st;
     unsorted = moved ? 1u : 0u;
   } else if (n > 0) {
     // (one pass makes the keys and the histogram the cells' bounds come from; a swarm in order needs no second)
     JB_HIP(hipMemsetAsync(m.flag, 0, sizeof(unsigned), ctx->stream));
-    JB_HIP(hipMemsetAsync(m.start, 0, sizeof(unsigned) * (size_t)nbins, ctx->stream));
-    hipLaunchKernelGGL(k_sort_count, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, m.key, m.start);
+    if ((st = count_cells(ctx, M, S, n, k, m)) != JB_COMPLETE) return st;
     hipLaunchKernelGGL(k_comb_unsorted, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)m.key, n, m.flag);
     JB_HIP(hipGetLastError());
     JB_HIP(hipMemcpyAsync(&unsorted, m.flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
@@ -2477,35 +2436,27 @@ extern "C" jb_status jb_evaluate_radiation_moments(jb_context *ctx, jb_mesh *mes
       if (st != JB_COMPLETE) return st;
     }
   }
-  if (unsorted) {   // for the schedule of jb_defrag_policy this is a sort, as a comb plan that sorted is
-    ctx->rate_ref = 0.0;
-    ctx->rate_before_sort = 0.0;
-    ctx->excess_ms = 0.0;
-    ctx->cycles_since_sort = 0;
-  }
+  if (unsorted) defrag_schedule_restart(ctx);   // for the policy this is a sort, as a comb plan that sorted is
   // the cells' bounds: the histogram of the keys of the swarm as it lies now, and its scan (what a move left in
   // the histogram's place are the cells' ends, not their starts)
   JB_HIP(hipMemsetAsync(m.stats, 0, sizeof(unsigned long long) * MS_N, ctx->stream));
   const bool counted = n > 0 && !by_id && !unsorted;   // the histogram of the order test stands
-  if (!counted) JB_HIP(hipMemsetAsync(m.start, 0, sizeof(unsigned) * (size_t)nbins, ctx->stream));
   if (n > 0) {
-    unsigned *sums = m.start + nbins;
-    if (!counted)
-      hipLaunchKernelGGL(k_sort_count, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, m.key, m.start);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(m.sort_tiles), dim3(kBlock), 0, ctx->stream, m.start, nbins, sums);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums, m.sort_tiles);
-    hipLaunchKernelGGL(k_scan_add, dim3(m.sort_tiles), dim3(kBlock), 0, ctx->stream, m.start, nbins, (const unsigned *)sums);
+    if (!counted && (st = count_cells(ctx, M, S, n, k, m)) != JB_COMPLETE) return st;
+    scan_u32(ctx, m.hist, k.nbins, m.sums);
+  } else {   // (every cell is empty)
+    JB_HIP(hipMemsetAsync(m.hist, 0, sizeof(unsigned) * (size_t)k.nbins, ctx->stream));
   }
   const int G = mom_group(n, cells);
   // (one workgroup per 256 slots, not a grid capped to the chip: chunk heads lie 64 waves apart in a long run, and
   // a strided walk would hand all of them to the same few waves; the hardware deals workgroups out as others end)
   if (n > 0)
     hipLaunchKernelGGL(k_mom_chunks, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, (const unsigned *)m.key,
-                       (const unsigned *)m.start, (unsigned)G, m.part, out_dev);
+                       (const unsigned *)m.hist, (unsigned)G, m.part, out_dev);
   const int gc = grid_for(ctx, cells);
   with_int<1, 2, 4, 8, 16, 32, 64>(G, [&](auto g) {
     hipLaunchKernelGGL(k_mom_cells<decltype(g)::value>, dim3(gc), dim3(kBlock), 0, ctx->stream, M, S,
-                       (const unsigned *)m.start, (const double *)m.part, out_dev, m.stats);
+                       (const unsigned *)m.hist, (const double *)m.part, out_dev, m.stats);
   });
   JB_HIP(hipGetLastError());
   if (report) {
@@ -2526,16 +2477,11 @@ extern "C" jb_status jb_evaluate_radiation_moments_host(jb_context *ctx, jb_mesh
   if (!ctx || !mesh || !out_host) return fail(JB_ERR_INVALID, "jb_evaluate_radiation_moments_host: null argument");
   JB_HIP(hipSetDevice(ctx->device));
   const size_t words = (size_t)jb_moments_words(mesh);
-  if (words > ctx->moments_words) {
-    if (ctx->moments_d) JB_HIP(hipFree(ctx->moments_d));
-    ctx->moments_d = nullptr;
-    ctx->moments_words = 0;
-    JB_HIP(hipMalloc(&ctx->moments_d, words * sizeof(double)));
-    ctx->moments_words = words;
-  }
-  const jb_status st = jb_evaluate_radiation_moments(ctx, mesh, swarm, ctx->moments_d, report);
+  jb_status st = dev_grow(ctx->moments, words * sizeof(double), "hipMalloc of the moments array");
   if (st != JB_COMPLETE) return st;
-  JB_HIP(hipMemcpyAsync(out_host, ctx->moments_d, words * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  st = jb_evaluate_radiation_moments(ctx, mesh, swarm, (double *)ctx->moments.p, report);
+  if (st != JB_COMPLETE) return st;
+  JB_HIP(hipMemcpyAsync(out_host, ctx->moments.p, words * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   JB_HIP(hipStreamSynchronize(ctx->stream));
   return JB_COMPLETE;
 }
@@ -2563,10 +2509,8 @@ static jb_status defrag_now(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view 
   (void)hipEventRecord(ctx->sort_ev[1], ctx->stream);
   ctx->sort_timed = true;
   ctx->sort_n = swarm->n;
+  defrag_schedule_restart(ctx);
   ctx->rate_before_sort = rate;
-  ctx->rate_ref = 0.0;
-  ctx->excess_ms = 0.0;
-  ctx->cycles_since_sort = 0;
   ++ctx->policy_sorts;
   *sorted = 1;
   return JB_COMPLETE;
@@ -2580,17 +2524,20 @@ extern "C" jb_status jb_release_scratch(jb_context *ctx) {
   ctx->scratch_d = nullptr;
   ctx->scratch_words = 0;
   ++ctx->scratch_gen;
-  if (ctx->step_send_d) JB_HIP(hipFree(ctx->step_send_d));
-  if (ctx->step_recv_d) JB_HIP(hipFree(ctx->step_recv_d));
-  if (ctx->step_gather_d) JB_HIP(hipFree(ctx->step_gather_d));
-  ctx->step_send_d = ctx->step_recv_d = nullptr;
-  ctx->step_send_cap = ctx->step_recv_cap = 0;
-  ctx->step_gather_d = nullptr;
-  ctx->step_gather_words = 0;
-  if (ctx->moments_d) JB_HIP(hipFree(ctx->moments_d));
-  ctx->moments_d = nullptr;
-  ctx->moments_words = 0;
+  for (DevBuf *b : {&ctx->step_send, &ctx->step_recv, &ctx->step_gather, &ctx->moments}) JB_HIP(dev_free(*b));
   return JB_COMPLETE;
+}
+
+// jb_defrag_policy: the sort's scratch is taken now -- or there is no room, and the policy backs off
+static void policy_take_scratch(jb_context *ctx, const jb_mesh *mesh, const jb_swarm_view *swarm) {
+  ctx->sort_scratch_tried = true;
+  const CellKeys k = cell_keys(mesh->dm.nblocks, mesh->dm.ntot, swarm->n);
+  if (k.over) return;   // (the sort itself will say so)
+  if (ensure_scratch(ctx, sort_layout(swarm->n, k.nbins, order_by_id(ctx)).words, /*slack=*/false) != JB_COMPLETE) {
+    fprintf(stderr, "jaybenne_amd: no room for the scratch records of DefragParticles (%s): the swarm stays unsorted\n", g_err);
+    (void)hipGetLastError();
+    ctx->min_interval = 256;
+  }
 }
 
 extern "C" jb_status jb_defrag_policy(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
@@ -2598,15 +2545,11 @@ extern "C" jb_status jb_defrag_policy(jb_context *ctx, jb_mesh *mesh, const jb_s
   if (!ctx || !mesh || !sorted) return fail(JB_ERR_INVALID, "null argument");
   if (mode < JB_DEFRAG_DECIDE_AND_SORT || mode > JB_DEFRAG_SORT_NOW) return fail(JB_ERR_INVALID, "unknown mode");
   *sorted = 0;
-  if (mode == JB_DEFRAG_SORT_NOW) {  // (the ranks have agreed: the cycle's times were taken by the DECIDE call)
-    JB_HIP(hipSetDevice(ctx->device));
-    jb_status st2 = check_swarm(swarm, "jb_defrag_policy");
-    if (st2 != JB_COMPLETE) return st2;
-    return defrag_now(ctx, mesh, swarm, ctx->last_rate, sorted);
-  }
   JB_HIP(hipSetDevice(ctx->device));
   jb_status st = check_swarm(swarm, "jb_defrag_policy");
   if (st != JB_COMPLETE) return st;
+  // (SORT_NOW: the ranks have agreed, and the cycle's times were taken by the DECIDE call)
+  if (mode == JB_DEFRAG_SORT_NOW) return defrag_now(ctx, mesh, swarm, ctx->last_rate, sorted);
   // time of this cycle's tracking kernels (the caller has synchronised: it knows the event count)
   double ms = 0.0;
   bool ok = !ctx->tev_overflow && ctx->tev_used > 0;
@@ -2656,18 +2599,7 @@ extern "C" jb_status jb_defrag_policy(jb_context *ctx, jb_mesh *mesh, const jb_s
   bool allocated_this_cycle = false;
   if (scratch_now) {
     allocated_this_cycle = true;
-    ctx->sort_scratch_tried = true;
-    const DevMesh &M0 = mesh->dm;
-    const unsigned long long nbins0 = (unsigned long long)M0.nblocks * (unsigned long long)M0.ntot + 1ull;
-    const unsigned long long ntiles0 = (nbins0 + kScanTile - 1) / kScanTile;
-    if (swarm->n < (1ll << 32) && nbins0 < (1ull << 32)) {
-      const size_t words = sort_scratch_words(ctx, swarm->n, (long long)nbins0, (int)ntiles0);
-      if (ensure_scratch(ctx, words, /*slack=*/false) != JB_COMPLETE) {
-        fprintf(stderr, "jaybenne_amd: no room for the scratch records of DefragParticles (%s): the swarm stays unsorted\n", g_err);
-        (void)hipGetLastError();
-        ctx->min_interval = 256;
-      }
-    }
+    policy_take_scratch(ctx, mesh, swarm);
   }
   if (ctx->rate_ref == 0.0 || rate < ctx->rate_ref) ctx->rate_ref = rate;
   const double excess_now = (rate - ctx->rate_ref) * (double)events_this_cycle;
@@ -2684,18 +2616,7 @@ extern "C" jb_status jb_defrag_policy(jb_context *ctx, jb_mesh *mesh, const jb_s
   if (p >= ctx->min_interval && rate > 1.015 * ctx->rate_ref &&
       excess_next * (double)p >= sort_ms + ctx->excess_ms) {
     if (!ctx->sort_scratch_tried) {   // (never asked for: this cycle takes the allocation, the next one the sort)
-      ctx->sort_scratch_tried = true;
-      const DevMesh &M1 = mesh->dm;
-      const unsigned long long nbins1 = (unsigned long long)M1.nblocks * (unsigned long long)M1.ntot + 1ull;
-      const unsigned long long ntiles1 = (nbins1 + kScanTile - 1) / kScanTile;
-      if (swarm->n < (1ll << 32) && nbins1 < (1ull << 32)) {
-        const size_t words = sort_scratch_words(ctx, swarm->n, (long long)nbins1, (int)ntiles1);
-        if (ensure_scratch(ctx, words, /*slack=*/false) != JB_COMPLETE) {
-          fprintf(stderr, "jaybenne_amd: no room for the scratch records of DefragParticles (%s): the swarm stays unsorted\n", g_err);
-          (void)hipGetLastError();
-          ctx->min_interval = 256;
-        }
-      }
+      policy_take_scratch(ctx, mesh, swarm);
       return JB_COMPLETE;
     }
     if (allocated_this_cycle && mode != JB_DEFRAG_SORT_NOW) return JB_COMPLETE;
@@ -2787,19 +2708,8 @@ extern "C" jb_status jb_unpack_incoming(jb_context *ctx, jb_mesh *mesh, jb_swarm
 
 // the rank x rank count matrix of jb_exchange (+ its pack offsets), in a buffer of the context's own
 static jb_status ensure_count_matrix(jb_context *ctx, int nranks) {
-  if (!ctx->xch_d || ctx->xch_ranks < nranks) {
-    if (ctx->xch_d) (void)hipFree(ctx->xch_d);
-    const size_t R = nranks > 64 ? (size_t)nranks : 64;
-    if (hipMalloc(&ctx->xch_d, R * (R + 8) * sizeof(unsigned long long)) == hipSuccess) {
-      ctx->xch_ranks = (int)R;
-    } else {
-      ctx->xch_d = nullptr;
-      ctx->xch_ranks = 0;
-      (void)hipGetLastError();
-      return fail(JB_ERR_HIP, "jb_exchange: hipMalloc of the count matrix failed");
-    }
-  }
-  return JB_COMPLETE;
+  const size_t R = nranks > 64 ? (size_t)nranks : 64;
+  return dev_grow(ctx->xch, R * (R + 8) * sizeof(unsigned long long), "jb_exchange: hipMalloc of the count matrix");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2864,7 +2774,7 @@ extern "C" jb_status jb_exchange(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *
   // in the gathered row of every later call: a rank-local failure must not leave the others in a collective)
   st = ensure_count_matrix(ctx, nranks);
   if (st != JB_COMPLETE) return st;
-  unsigned long long *matrix_d = ctx->xch_d;
+  unsigned long long *matrix_d = (unsigned long long *)ctx->xch.p;
   if (tr->all_gather_u64(tr->handle, (const uint64_t *)per_rank, (uint64_t *)matrix_d, row, (void *)ctx->stream) != 0)
     return fail(JB_ERR_HIP, "jb_exchange: the transport's all-gather of the record counts failed");
   // 3. ... and read back ONCE per call: nranks (nranks + 3) words
@@ -3071,6 +2981,12 @@ extern "C" jb_status jb_fill_cells(jb_context *ctx, jb_mesh *mesh, int field, in
 // ------------------------------------------------------------------------------------------------
 // Energy ledger (jb_kernel_ledger.hpp): sweeps that write per-workgroup partial sums, one workgroup that adds
 // them in a fixed order into the running ledger on the device, one read-back when the cycle closes.
+// the buffer of jb_ledger_reduce: a row [status | ledger] of this rank's, then one of every rank's
+static jb_status ledger_gather_room(jb_context *ctx, int nranks) {
+  return dev_grow(ctx->ledger_gather, (size_t)kLedgerGatherRow * (size_t)(nranks + 1) * sizeof(unsigned long long),
+                  "hipMalloc of the ledger's gather buffer");
+}
+
 extern "C" jb_status jb_ledger_enable(jb_context *ctx, int on) {
   if (!ctx) return fail(JB_ERR_INVALID, "jb_ledger_enable: null argument");
   JB_HIP(hipSetDevice(ctx->device));
@@ -3079,12 +2995,11 @@ extern "C" jb_status jb_ledger_enable(jb_context *ctx, int on) {
     JB_HIP(hipMalloc(&ctx->ledger_d, ((size_t)kLedgerHead + (size_t)parts * kLedgerStride) * sizeof(unsigned long long)));
     ctx->ledger_parts = parts;
   }
-  if (on && !ctx->ledger_gather_d) {
-    // (taken here, for any number of ranks the step call accepts: jb_ledger_reduce then has nothing left that
-    // can fail on one rank alone before its collective)
-    const size_t words = (size_t)kLedgerGatherRow * (size_t)(kRankEnd + 1);
-    JB_HIP(hipMalloc(&ctx->ledger_gather_d, words * sizeof(unsigned long long)));
-    ctx->ledger_gather_words = words;
+  // (taken here, for any number of ranks the step call accepts: jb_ledger_reduce then has nothing left that
+  // can fail on one rank alone before its collective)
+  if (on && !ctx->ledger_gather.p) {
+    const jb_status st = ledger_gather_room(ctx, kRankEnd);
+    if (st != JB_COMPLETE) return st;
   }
   if (on) JB_HIP(hipMemsetAsync(ctx->ledger_d, 0, kLedgerHead * sizeof(unsigned long long), ctx->stream));
   ctx->ledger_on = on != 0;
@@ -3185,15 +3100,9 @@ static jb_status ledger_reduce(jb_context *ctx, const jb_exchange_transport *tr,
     return fail(JB_ERR_INVALID, "jb_ledger_reduce: %d ranks need a transport with all_gather_u64", nranks);
   if (nranks == 1) return local;
   JB_HIP(hipSetDevice(ctx->device));
-  const size_t words = (size_t)kLedgerGatherRow * (size_t)(nranks + 1);
-  if (ctx->ledger_gather_words < words) {
-    if (ctx->ledger_gather_d) (void)hipFree(ctx->ledger_gather_d);
-    ctx->ledger_gather_d = nullptr;
-    ctx->ledger_gather_words = 0;
-    JB_HIP(hipMalloc(&ctx->ledger_gather_d, words * sizeof(unsigned long long)));
-    ctx->ledger_gather_words = words;
-  }
-  unsigned long long *in_d = ctx->ledger_gather_d, *all_d = ctx->ledger_gather_d + kLedgerGatherRow;
+  const jb_status gst = ledger_gather_room(ctx, nranks);
+  if (gst != JB_COMPLETE) return gst;
+  unsigned long long *in_d = (unsigned long long *)ctx->ledger_gather.p, *all_d = in_d + kLedgerGatherRow;
   std::vector<unsigned long long> mine((size_t)kLedgerGatherRow, 0), rows((size_t)kLedgerGatherRow * (size_t)nranks, 0);
   mine[0] = local == JB_COMPLETE ? 0ull : (unsigned long long)(-(long long)local);
   memcpy(&mine[1], inout, sizeof *inout);
@@ -3494,7 +3403,7 @@ static jb_status radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *s
       if (st != JB_COMPLETE) return st;
     }
     if (bs_on) {
-      st = jb_source_boundary_fill(ctx, mesh, swarm, t_start, dt, nper_bs.data(), ctx->bs_prefix_d, slot_bs.data(),
+      st = jb_source_boundary_fill(ctx, mesh, swarm, t_start, dt, nper_bs.data(), (int32_t *)ctx->bs_prefix.p, slot_bs.data(),
                                    ids_bs.data());
       if (st != JB_COMPLETE) return st;
     }
@@ -3557,18 +3466,11 @@ extern "C" jb_status jb_radiation_step(jb_context *ctx, jb_mesh *mesh, jb_swarm_
 // step for step what jaybenne_amd/jaybenne.py drives through the task entry points.
 
 // a hand-off record buffer of the library's own, grown to at least `records` (its contents are not kept)
-static jb_status ensure_records(long long **buf, long long *cap, long long records) {
-  if (*buf && *cap >= records) return JB_COMPLETE;
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr;
-  *cap = 0;
-  if (hipMalloc(buf, (size_t)records * kRecWords * sizeof(long long)) != hipSuccess) {
-    *buf = nullptr;
-    (void)hipGetLastError();
-    return fail(JB_ERR_HIP, "hipMalloc of a hand-off buffer of %lld records failed", records);
-  }
-  *cap = records;
-  return JB_COMPLETE;
+static long long records_cap(const DevBuf &b) { return (long long)(b.bytes / (kRecWords * sizeof(long long))); }
+static jb_status ensure_records(DevBuf &b, long long records) {
+  char what[96];
+  snprintf(what, sizeof what, "hipMalloc of a hand-off buffer of %lld records", records);
+  return dev_grow(b, (size_t)records * kRecWords * sizeof(long long), what);
 }
 
 // room for n_slots particles: the host's reserve, if it gave one
@@ -3621,18 +3523,11 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
     // the gather buffer first (without it this rank could not say anything: the one failure it cannot
     // share), then the rest of what the step allocates
     const size_t words = row * (size_t)(nranks + 1);
-    if (multi && ctx->step_gather_words < words) {
-      if (ctx->step_gather_d) (void)hipFree(ctx->step_gather_d);
-      ctx->step_gather_words = 0;
-      if (hipMalloc(&ctx->step_gather_d, words * sizeof(unsigned long long)) != hipSuccess) {
-        ctx->step_gather_d = nullptr;
-        (void)hipGetLastError();
-        return fail(JB_ERR_HIP, "jb_radiation_step_ranks: hipMalloc of the gather buffer failed");
-      }
-      ctx->step_gather_words = words;
-    }
-    jb_status st = check_swarm(swarm, "jb_radiation_step_ranks");
-    if (st != JB_COMPLETE) return st;
+    jb_status st = JB_COMPLETE;
+    if (multi && (st = dev_grow(ctx->step_gather, words * sizeof(unsigned long long),
+                                "jb_radiation_step_ranks: hipMalloc of the gather buffer")) != JB_COMPLETE)
+      return st;
+    if ((st = check_swarm(swarm, "jb_radiation_step_ranks")) != JB_COMPLETE) return st;
     if (M.rank != rank)
       return fail(JB_ERR_INVALID, "jb_radiation_step_ranks: comm rank %d is not the mesh view's rank %d", rank, M.rank);
     if (*cycle >= (1u << 19) - 1u)   // (SourceEpoch, as jb_radiation_step)
@@ -3641,11 +3536,11 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
       return fail(JB_ERR_INVALID, "emission source needs the prefix workspace");
     if (multi) {
       if ((st = ensure_count_matrix(ctx, nranks)) != JB_COMPLETE) return st;
-      if (!ctx->step_send_d || !ctx->step_recv_d) {
+      if (!ctx->step_send.p || !ctx->step_recv.p) {
         // (JB_HANDOFF_MIN_RECORDS: a small first size, so that the tests walk through the capacity protocol)
         const long long start = ctx->min_records > 0 ? ctx->min_records : (swarm->n / 16 > 4096 ? swarm->n / 16 : 4096);
-        if ((st = ensure_records(&ctx->step_send_d, &ctx->step_send_cap, start)) != JB_COMPLETE) return st;
-        if ((st = ensure_records(&ctx->step_recv_d, &ctx->step_recv_cap, start)) != JB_COMPLETE) return st;
+        if ((st = ensure_records(ctx->step_send, start)) != JB_COMPLETE) return st;
+        if ((st = ensure_records(ctx->step_recv, start)) != JB_COMPLETE) return st;
       }
     }
     if ((st = jb_update_derived_transport_fields(ctx, mesh, dt)) != JB_COMPLETE) return st;
@@ -3670,7 +3565,7 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
     return JB_COMPLETE;
   };
   const jb_status local = local_part();
-  if (multi && !ctx->step_gather_d) return done(local);
+  if (multi && !ctx->step_gather.p) return done(local);
   // the first collective: [status | new photons per global block] of every rank
   std::vector<unsigned long long> mine(row, 0), all(row * (size_t)nranks, 0);
   if (local != JB_COMPLETE) {
@@ -3680,7 +3575,7 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
       mine[1 + (size_t)mesh->gid_host[b]] = (unsigned long long)nper[b] + (unsigned long long)nper_bs[b];
   }
   if (multi) {
-    unsigned long long *in_d = ctx->step_gather_d, *all_d = ctx->step_gather_d + row;
+    unsigned long long *in_d = (unsigned long long *)ctx->step_gather.p, *all_d = in_d + row;
     JB_HIP(hipMemcpyAsync(in_d, mine.data(), row * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
     if (tr->all_gather_u64(tr->handle, (const uint64_t *)in_d, (uint64_t *)all_d, (int)row, (void *)ctx->stream) != 0)
       return done(fail(JB_ERR_HIP, "jb_radiation_step_ranks: the transport's all-gather of the source counts failed"));
@@ -3710,7 +3605,7 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
       if (st != JB_COMPLETE) return done(st);
     }
     if (bs_on) {
-      st = jb_source_boundary_fill(ctx, mesh, swarm, t_start, dt, nper_bs.data(), ctx->bs_prefix_d,
+      st = jb_source_boundary_fill(ctx, mesh, swarm, t_start, dt, nper_bs.data(), (int32_t *)ctx->bs_prefix.p,
                                    pl.slot_base_boundary.data(), pl.id_base_boundary.data());
       if (st != JB_COMPLETE) return done(st);
     }
@@ -3739,14 +3634,14 @@ extern "C" jb_status jb_radiation_step_ranks(jb_context *ctx, jb_mesh *mesh, jb_
       if (!multi) { finished = true; break; }   // (every block crossing was resolved in flight)
       int64_t nsent = 0, nrecv = 0, moved = 0, xf = first, xl = last;
       for (int call = 1;; ++call) {
-        st = jb_exchange(ctx, mesh, swarm, xf, xl, rank, nranks, tr, (int64_t *)ctx->step_send_d, ctx->step_send_cap,
-                         (int64_t *)ctx->step_recv_d, ctx->step_recv_cap, &nsent, &nrecv, &moved);
+        st = jb_exchange(ctx, mesh, swarm, xf, xl, rank, nranks, tr, (int64_t *)ctx->step_send.p, records_cap(ctx->step_send),
+                         (int64_t *)ctx->step_recv.p, records_cap(ctx->step_recv), &nsent, &nrecv, &moved);
         if (st != JB_ERR_CAPACITY || call == kExchangeCalls) break;
         // The verdict is the same on every rank: each makes the room IT lacks and all call again.  A failure
         // to grow leaves the room short, and the next verdict -- again the same everywhere -- says so.
         ++rep.capacity_rounds;
-        if (nsent > ctx->step_send_cap) (void)ensure_records(&ctx->step_send_d, &ctx->step_send_cap, nsent * 3 / 2 + 16);
-        if (nrecv > ctx->step_recv_cap) (void)ensure_records(&ctx->step_recv_d, &ctx->step_recv_cap, nrecv * 3 / 2 + 16);
+        if (nsent > records_cap(ctx->step_send)) (void)ensure_records(ctx->step_send, nsent * 3 / 2 + 16);
+        if (nrecv > records_cap(ctx->step_recv)) (void)ensure_records(ctx->step_recv, nrecv * 3 / 2 + 16);
         if (swarm->n + nrecv > swarm->capacity) {
           // close the holes earlier departures left; what still has to go is found by its status
           if ((st = jb_remove_marked_particles(ctx, swarm)) != JB_COMPLETE) return done(st);

@@ -41,8 +41,7 @@
 
 namespace jb {
 
-constexpr int kMomSums = kMoments - 1;   // the rounded sums: components 1 .. 11 (component 0 is the count)
-enum { MS_COUNTED = 0, MS_NONEMPTY, MS_LONGEST, MS_N };
+// (kMomSums, MS_*: jb_scratch_layout.hpp)
 constexpr int kMomRows = 8;   // rows of 64 slots a wave of k_mom_chunks has loads in flight for: 16 KB
 
 __device__ __forceinline__ double mom_load(const double *p) { return __builtin_nontemporal_load(p); }

@@ -37,7 +37,7 @@ namespace jb {
 
 constexpr int kOrderItems = 8;                    // rounds of a wave
 constexpr int kOrderWaveSlots = 64 * kOrderItems; // consecutive slots of a wave
-static_assert(kOrderTile == kBlock * kOrderItems && kOrderScanTile == kScanTile && kOrderDigits == kBlock,
+static_assert(kOrderTile == kBlock * kOrderItems && kOrderDigits == kBlock,
               "jb_order_plan.hpp sizes the counts for these tiles; a thread per digit combines the waves' counts");
 
 // the read-back of k_order_check

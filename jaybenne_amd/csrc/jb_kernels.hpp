@@ -22,6 +22,7 @@
 
 #include "jb_device.hpp"
 #include "jb_invariants.hpp"   // the checked build's JB_INV_* call sites (nothing without JB_INVARIANTS)
+#include "jb_scratch_layout.hpp"   // kSortRecWords, kMomSums, kCombParts: the sizes kernels and layouts share
 #include "jb_scaffold.hpp"     // queue constants and cursor, LDS tally, outcome counts: shared by the tracking kernels
 
 namespace jb {
@@ -1544,7 +1545,8 @@ __global__ void __launch_bounds__(kBlock)
 
 // In-place exclusive scan of `data` in tiles of kScanTile elements (one workgroup each); the tile
 // totals go to `sums`, which k_scan_sums scans and k_scan_add adds back.
-constexpr int kScanItems = 8, kScanTile = kBlock * kScanItems;
+constexpr int kScanItems = 8;
+static_assert(kScanTile == kBlock * kScanItems, "jb_limits.hpp restates the scan's tile");
 __global__ void __launch_bounds__(kBlock) k_scan_tiles(unsigned *data, long long n, unsigned *sums) {
   __shared__ unsigned wave_tot[kBlock / 64];
   const long long base = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
@@ -1624,7 +1626,7 @@ __global__ void __launch_bounds__(kBlock) k_scan_add(unsigned *data, long long n
 //   k_sort_pack:   slot s, read in order -> record at the photon's new position (8 x 16 B, one line)
 //   k_sort_unpack: records in order -> the swarm arrays, written in order -- the SAME arrays
 // record: {x, y} {z, vx} {vy, vz} {t, w} {e, id} {rng, ip | jp << 32} {kp | blk << 32, status} {-, -}
-constexpr int kSortRecWords = 16;  // 8-byte words per record
+// (kSortRecWords 8-byte words per record: jb_scratch_layout.hpp)
 // (each record is written by ONE store instruction, whole: the wave stages its 64 records in LDS and
 // eight lanes then store the eight 16-byte pieces of a record together.  With every lane storing
 // its own record piece by piece -- eight instructions that each touch 64 different lines -- the

@@ -19,6 +19,9 @@ constexpr int kDepositLds = kLdsTally;
 constexpr int kMaxClasses = 256;            // 16 KB of LDS per workgroup at most
 constexpr int kLdsRecCells = 256;    // cells whose step records k_ddmc_all<.., GATHER 2> copies to LDS (jb_kernel_ddmc.hpp)
 constexpr int kLdsCodeCells = 1024;  // cells whose codes k_ddmc_q<.., LCODES> copies to LDS (jb_kernel_ddmc_q.hpp)
+// elements a workgroup of the scan kernels takes (k_scan_*, jb_kernels.hpp: kBlock threads x kScanItems); the scratch
+// layouts (jb_order_plan.hpp, jb_scratch_layout.hpp) size the scans' tile sums by it
+constexpr int kScanTile = 2048;
 // radiation moments (jb_kernel_moments.hpp): components per cell (JB_MOMENTS), and the slots of a cell's run that
 // one wave sums -- a run is cut into chunks of this many slots from its head (a power of two, a multiple of 64)
 constexpr int kMoments = 12;

@@ -6,11 +6,12 @@
 
 #include <cstddef>
 
+#include "jb_limits.hpp"
+
 namespace jb {
 
 constexpr int kOrderTile = 2048;      // slots per workgroup of a radix pass (256 threads x 8: jb_kernel_order.hpp)
 constexpr int kOrderDigits = 256;     // 8-bit digits
-constexpr int kOrderScanTile = 2048;  // kScanTile of jb_kernels.hpp (the counts are scanned by k_scan_*)
 constexpr int kOrderMaxPasses = 12;   // 8 of the id + 4 of the cell key
 
 // The sort key is (32-bit cell key, 64-bit id), taken as three 32-bit words: a pass carries (word, slot index)
@@ -80,7 +81,7 @@ inline OrderLayout order_layout(long long n, size_t start) {
   if (n < 0) n = 0;
   L.tiles = (n + kOrderTile - 1) / kOrderTile;
   L.ncnt = (long long)kOrderDigits * L.tiles;
-  L.scan_tiles = (L.ncnt + kOrderScanTile - 1) / kOrderScanTile;
+  L.scan_tiles = (L.ncnt + kScanTile - 1) / kScanTile;   // (the counts are scanned by k_scan_*)
   size_t o = start;
   L.pairs[0] = o; o += (size_t)n;
   L.pairs[1] = o; o += (size_t)n;

@@ -384,6 +384,22 @@ def test_three_ways_to_step_agree_bit_for_bit(gpu_device, monkeypatch):
     assert exact > 0, "neither the tally field nor the census slot order repeated in any of the runs"
 
 
+def test_a_cycle_after_release_scratch_gives_the_oracles_ledger(gpu_device):
+    """jb_release_scratch between two ledger-on cycles: the ledger's own buffers stay, the scratch memory is taken
+    again, and both cycles' ledgers are the oracle's"""
+    from jaybenne_amd import _lib
+    cid, bset = "G3U-imc", "S1"
+    want = lc.oracle_ledgers(cid, bset, 2)
+    drv, _ = _driver(cid, bset, gpu_device)
+    md = drv.md
+    drv.Step()
+    _compare_ledger(md.ledger, want[0], 1e-12)
+    md._sync_stream()
+    _lib.check(md.lib.jb_release_scratch(md.pkg.ctx))
+    drv.Step()
+    _compare_ledger(md.ledger, want[1], 1e-12)
+
+
 # ---- 4. several ranks --------------------------------------------------------------------------
 RANKS = [("G3S-imc", "S3", 2, "blocks", "step"), ("G3S-ddmc", "S1", 4, "blocks", "step"),
          ("G3S-imc", "S3", 2, "blocks", "c"), ("G3S-ddmc", "S1", 2, "replicated", "c")]

@@ -150,6 +150,107 @@ def test_null_arguments_are_refused(gpu_device, views):
     assert md.lib.jb_moments_words(md.handle) == 12 * g.nblocks * g.ncell
 
 
+# ---- the sort, the comb and the moments in one scratch memory ---------------------------------------------
+# One context runs a defrag sort, a comb plan + apply and a moments evaluation: the three share the library's scratch
+# memory (jaybenne_amd/csrc/jb_scratch_layout.hpp).  A mesh of 13 histogram bins and one of 2054 -- more than a scan
+# tile of 2048 --, swarm sizes on both sides of a scan tile and of a moments chunk, odd and even (the 4-byte arrays
+# are packed in pairs), both cell orders: each call against its numpy model.
+NX1, MB1 = "parthenon/mesh/nx1", "parthenon/meshblock/nx1"
+TILE_MESHES = {"8 cells": ("stepdiff", {NX1: 8, MB1: 8, NP: 64}), "2049 cells": ("stepdiff", {NX1: 2049, MB1: 2049, NP: 64})}
+TILE_COMB = {"8 cells": (70, 32), "2049 cells": (3, 2)}          # (T, K): some 260 | 1 .. 2 photons per cell
+TILE_N = (2047, 2048, 2049, 4097)
+
+
+def _tile_swarm(mesh, n):
+    """n ACTIVE photons with hashed ids in hashed cells (tests/test_gpu_cell_order.py), one in 97 forty times as
+    heavy: on the coarse mesh the comb keeps several copies of some"""
+    from test_gpu_cell_order import _edge_swarm
+    sw = _edge_swarm(mesh, n, True, salt=11 * n)
+    sw["w"][::97] *= 40.0
+    return sw
+
+
+def _sort_comb_moments(drv, g, name, n, order, device):
+    import comb_model as cm
+    from jaybenne_amd import _lib
+    from test_gpu_cell_order import NEW_IDS
+    from test_gpu_comb import EPOCH, _apply, _plan, _same
+    from test_gpu_swarm_ops import _defrag
+    md, mesh = drv.md, drv.mesh
+    what = (name, n, order)
+    T, K = TILE_COMB[name]
+    seed = int(drv.pin.GetOrAddInteger("jaybenne", "seed", 123))
+    sw = _tile_swarm(mesh, n)
+    canon = mm.canonical(g, sw, n)
+    assert not mm.in_order(g, sw, n)
+    # the sort
+    _upload(md, sw, device)
+    _defrag(md)
+    got = _download(md, n)
+    assert md.n == n and som.sorted_failures(g, sw, got, n) == [], what
+    if order == "id":
+        assert som.differing(got, canon) == [], what
+    # the comb: the plan sorts; the model works on the swarm as the plan left it
+    _upload(md, mm.shuffle(sw, 3), device)
+    st, plan = _plan(md, T, K)
+    assert st == _lib.JB_COMPLETE and plan.sorted == 1, (what, md.lib.jb_last_error())
+    g0 = _download(md, n)
+    assert som.sorted_failures(g, sw, g0, n) == [], what
+    if order == "id":
+        assert som.differing(g0, canon) == [], what
+    want, info = cm.comb_swarm(mesh, md.resident_gids, g0, n, T, K, seed, EPOCH, NEW_IDS, sort=False)
+    assert info["cells_combed"] > 0 and min(info["margins"].values()) >= 1e-9, what
+    assert (plan.n_before, plan.n_after, plan.n_new_ids, plan.cells_combed, plan.max_per_cell) == \
+        (n, info["n_after"], info["n_new_ids"], info["cells_combed"], info["max_per_cell"]), what
+    st, rep = _apply(md, NEW_IDS)
+    assert st == _lib.JB_COMPLETE and (rep.n_after, rep.n_new_ids) == (plan.n_after, plan.n_new_ids), what
+    assert md.n == info["n_after"]
+    g1 = _download(md, md.n)
+    assert _same(g1, want, [q for q in cm.SWARM_KEYS if q != "w"]), what
+    assert np.allclose(g1["w"], want["w"], rtol=1e-13, atol=0), what     # (W of a cell by two orders of summation)
+    # the moments: the call sorts
+    _, after = _against_the_model(md, g, mm.shuffle(sw, 5), what)
+    if order == "id":
+        assert som.differing(after, canon) == [], what
+
+
+@pytest.mark.parametrize("order", ["any", "id"])
+@pytest.mark.parametrize("n", TILE_N)
+@pytest.mark.parametrize("name", list(TILE_MESHES))
+def test_sort_comb_and_moments_share_one_scratch(gpu_device, views, name, n, order):
+    drv, g = views(TILE_MESHES[name])
+    drv.md.cell_order = order
+    try:
+        _sort_comb_moments(drv, g, name, n, order, gpu_device)
+    finally:
+        drv.md.cell_order = "any"
+
+
+def test_the_scratch_changes_hands(gpu_device, views):
+    """A comb plan lies in the scratch memory until it is applied: a moments evaluation in between, or
+    jb_release_scratch, takes the memory -- the apply then finds no plan.  After the release the three calls work
+    as before."""
+    from jaybenne_amd import _lib
+    from test_gpu_comb import _apply, _plan
+    name, n = "8 cells", 2049
+    drv, g = views(TILE_MESHES[name])
+    md = drv.md
+    T, K = TILE_COMB[name]
+    for taker in ("moments", "release"):
+        _upload(md, _tile_swarm(drv.mesh, n), gpu_device)
+        st, plan = _plan(md, T, K)
+        assert st == _lib.JB_COMPLETE and plan.n_after < n, md.lib.jb_last_error()
+        if taker == "moments":
+            _moments(md)
+        else:
+            md._sync_stream()
+            _check(md, md.lib.jb_release_scratch(md.pkg.ctx))
+        st, _ = _apply(md)
+        assert st == _lib.JB_ERR_INVALID and b"no plan for this swarm" in md.lib.jb_last_error(), taker
+        assert md.n == n
+    _sort_comb_moments(drv, g, name, n, "any", gpu_device)
+
+
 # ---- slot order -------------------------------------------------------------------------------------------
 def _mixed(g):
     return mm.run_swarm(g, [65, 4097, 1, 2 * mm.CHUNK + 1, 64, 700, 2, 63], extras=mm.EXTRAS)

@@ -232,13 +232,13 @@ def test_iteration_limit_returns_iterate_on_every_rank(gpu_device, tmp_path):
         assert int(p["cycle"][0]) == 1
 
 
-def test_one_rank_equals_jb_radiation_step(gpu_device):
-    """nranks = 1, transport = NULL: jb_radiation_step_ranks is jb_radiation_step -- two cycles of
-    stepdiff_smr_hybrid, photons bit for bit (by id), every field to the order of the tally atomics."""
+def _one_rank_runs(gpu_device):
+    """run(handoff, release=False): two cycles of stepdiff_smr_hybrid on one rank, by jb_radiation_step_ranks
+    ("step") or by jb_radiation_step ("c"); release: jb_release_scratch between the two cycles"""
     from jaybenne_amd import _lib, mcblock
     over = dict(CASES[3][1])
 
-    def run(handoff):
+    def run(handoff, release=False):
         os.environ["JB_HANDOFF"] = handoff
         try:
             drv = mcblock.McblockDriver(load_deck("stepdiff_smr_hybrid", over), device=gpu_device, capacity_factor=2.0)
@@ -246,7 +246,10 @@ def test_one_rank_equals_jb_radiation_step(gpu_device):
             os.environ.pop("JB_HANDOFF", None)
         drv.md.defrag_interval = 0
         md = drv.md
-        for _ in range(2):
+        for cycle in range(2):
+            if release and cycle == 1:
+                md._sync_stream()
+                _lib.check(md.lib.jb_release_scratch(md.pkg.ctx))
             if handoff == "step":
                 assert drv.Step() == drv.jb.TaskStatus.complete
                 assert md.step_report.transport_iterations == 1
@@ -262,11 +265,33 @@ def test_one_rank_equals_jb_radiation_step(gpu_device):
         fields = {k: v.cpu().numpy() for k, v in md.fields.items()}
         return md.get_swarm(), fields, md.next_id, md.cycle
 
+    return run
+
+
+def test_one_rank_equals_jb_radiation_step(gpu_device):
+    """nranks = 1, transport = NULL: jb_radiation_step_ranks is jb_radiation_step -- two cycles of
+    stepdiff_smr_hybrid, photons bit for bit (by id), every field to the order of the tally atomics."""
+    run = _one_rank_runs(gpu_device)
     sa, fa, ida, ca = run("step")
     sb, fb, idb, cb = run("c")
     assert (ida, ca) == (idb, cb) and ca == 2
     oa, ob = np.argsort(sa["id"]), np.argsort(sb["id"])
     assert len(oa) == len(ob) and np.array_equal(sa["id"][oa], sb["id"][ob])
+    for k in sa:
+        assert np.array_equal(sa[k][oa], sb[k][ob]), k
+    for k in fa:
+        np.testing.assert_allclose(fa[k], fb[k], rtol=1e-12, atol=0, err_msg=k)
+
+
+def test_one_rank_step_after_release_scratch(gpu_device):
+    """jb_release_scratch between two cycles lets go of the scratch memory and the step's own buffers: the next
+    jb_radiation_step_ranks takes them again and gives the photons of the run that kept them, bit for bit (by id)."""
+    run = _one_rank_runs(gpu_device)
+    sa, fa, ida, ca = run("step")
+    sb, fb, idb, cb = run("step", release=True)
+    assert (ida, ca) == (idb, cb) and ca == 2
+    oa, ob = np.argsort(sa["id"]), np.argsort(sb["id"])
+    assert len(oa) == len(ob) > 0 and np.array_equal(sa["id"][oa], sb["id"][ob])
     for k in sa:
         assert np.array_equal(sa[k][oa], sb[k][ob]), k
     for k in fa:
