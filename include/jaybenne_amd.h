@@ -367,8 +367,13 @@ int jb_get_arithmetic(const jb_context *ctx);
  * phase, DDMC phase, remainder); "" before the first launch.  The pointer is valid until the next
  * transport call on this mesh or until the mesh is destroyed.  jb_mesh_exact_geometry: 1 if every
  * resident block has power-of-two cell widths and a lower corner that is a whole number of them
- * (and the per-cell arrays of the resident blocks span less than 4 GiB). */
+ * (and the per-cell arrays of the resident blocks span less than 4 GiB).
+ * jb_last_transport_grid: the largest number of workgroups any persistent tracking launch of the
+ * last transport call on this mesh used (a call makes up to three launches), 0 before the first.
+ * JB_TRANSPORT_MAX_BLOCKS=k in the environment at jb_initialize caps it at k (a test aid: the
+ * results do not depend on the grid; unset or <= 0: no cap). */
 const char *jb_last_transport_variant(const jb_mesh *mesh);
+int jb_last_transport_grid(const jb_mesh *mesh);
 int jb_mesh_exact_geometry(const jb_mesh *mesh);
 /* All-DDMC meshes: the number of DISTINCT step records UpdateDerivedTransportFields found among the
  * resident cells this cycle, as the last jb_transport_photons_ddmc call read it back (0 before the

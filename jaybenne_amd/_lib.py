@@ -268,6 +268,7 @@ PROTOTYPES = {
     "jb_transport_photons_ddmc": (_int, [_vp, _vp, C.POINTER(SwarmView), _f64, _f64, _i64, _i64,
                                          _int]),
     "jb_last_transport_variant": (C.c_char_p, [_vp]),
+    "jb_last_transport_grid": (_int, [_vp]),
     "jb_mesh_exact_geometry": (_int, [_vp]),
     "jb_mesh_ddmc_classes": (_int, [_vp]),
     "jb_get_transport_stats": (_int, [_vp, C.POINTER(TransportStats), _int]),

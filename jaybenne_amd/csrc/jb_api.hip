@@ -120,6 +120,8 @@ struct jb_context {
   // order of the photons within a cell behind a sort (JB_CELL_ORDER=id at jb_initialize, or jb_set_cell_order)
   int cell_order = JB_CELL_ORDER_ANY;
   int blocks_per_cu_env = 0;  // JB_TRANSPORT_BLOCKS_PER_CU at jb_initialize (tuning aid), 0 = occupancy query
+  int max_blocks_env = 0;     // JB_TRANSPORT_MAX_BLOCKS at jb_initialize (tests: many photons per lane), <= 0 = no cap
+  int grid_max = 0;           // largest grid launch_persistent used since transport_impl last cleared it
   bool no_ddmc_all = false;   // JB_NO_DDMC_ALL=1 at jb_initialize (tests: k_hybrid on all-DDMC meshes)
   int ddmc_lds_codes = 1;          // JB_DDMC_LDS_CODES=0: k_ddmc_q gathers the cell codes from device memory on any mesh (tests, A/B)
   int ddmc_queues = 1;             // JB_DDMC_QUEUES=0: k_ddmc_all instead of k_ddmc_q where both apply (tests, A/B)
@@ -196,6 +198,7 @@ struct jb_mesh {
   // multiply-adds of the BYTE strides 8 ni and 8 ni nj: both have to stay below 2^23
   bool cell_ok = false;
   char last_variant[64] = "";  // variant_name of the last transport call's plan (jb_last_transport_variant)
+  int last_grid = 0;           // ... and the largest grid of its persistent launches (jb_last_transport_grid)
   const DevMesh *dm_dev = nullptr;  // copy of dm in device memory (k_hybrid reads the view through it)
   const int *nbr_dq = nullptr;      // k_imc_cell: change of the cell's byte offset per (block, face) crossing
   bool uniform_geom = false;        // every resident block has the cell widths of block 0 (k_imc_cell<.., UNIFORM>)
@@ -519,6 +522,7 @@ extern "C" jb_status jb_initialize(const jb_params *params, const jb_eos *eos,
   if (const char *e = getenv("JB_SOURCE_ALLOCATION"))
     ctx->source_allocation = strcmp(e, "energy") == 0 ? JB_ALLOC_ENERGY : JB_ALLOC_UNIFORM;
   if (const char *e = getenv("JB_TRANSPORT_BLOCKS_PER_CU")) ctx->blocks_per_cu_env = atoi(e);
+  if (const char *e = getenv("JB_TRANSPORT_MAX_BLOCKS")) ctx->max_blocks_env = atoi(e);
   if (const char *e = getenv("JB_NO_DDMC_ALL")) ctx->no_ddmc_all = e[0] == '1';
   if (const char *e = getenv("JB_NO_IMC_CELL")) ctx->no_imc_cell = e[0] == '1';
   if (const char *e = getenv("JB_COOP_GATHER")) ctx->coop_gather = e[0] == '1' ? 1 : (e[0] == '2' ? 2 : (e[0] == '4' ? 4 : 0));  // (tests, A/B runs)
@@ -1533,7 +1537,9 @@ using kernel_c = std::integral_constant<decltype(Kernel), Kernel>;
 
 // The tracking kernels are persistent (waves draw particles from queues until they are empty), so the grid
 // is exactly what the chip holds at once: more workgroups would only start when the queues
-// are already drained.  JB_TRANSPORT_BLOCKS_PER_CU overrides the occupancy query (tuning aid).
+// are already drained.  JB_TRANSPORT_BLOCKS_PER_CU overrides the occupancy query (tuning aid);
+// JB_TRANSPORT_MAX_BLOCKS caps the grid behind every policy (tests: a few workgroups follow the whole swarm, so
+// every lane is refilled many times; placement only affects speed, never results).
 enum class Occupancy {
   cached,           // one query per kernel instantiation and process (the kernels without dynamic LDS)
   per_launch,       // the dynamic LDS -- tally and record table of a small mesh -- changes with the mesh: ask per launch
@@ -1553,6 +1559,8 @@ static void launch_persistent(jb_context *ctx, long long n, size_t dyn_lds, Occu
     if (policy == Occupancy::per_launch_cap3 && occ > 3) occ = 3;
     g = grid_for(ctx, n, ctx->blocks_per_cu_env > 0 ? ctx->blocks_per_cu_env : occ);
   }
+  if (ctx->max_blocks_env > 0 && g > ctx->max_blocks_env) g = ctx->max_blocks_env;
+  if (g > ctx->grid_max) ctx->grid_max = g;
   hipLaunchKernelGGL(Kernel, dim3(g), dim3(kBlock), dyn_lds, ctx->stream, args...);
 }
 
@@ -1781,9 +1789,11 @@ static jb_status transport_impl(jb_context *ctx, jb_mesh *mesh, const jb_swarm_v
   } else {
     ctx->tev_overflow = true;
   }
+  ctx->grid_max = 0;
   with_int<1, 2, 3>(M.ndim, [&](auto nd) {
     st = launch_transport<decltype(nd)::value>(ctx, mesh, S, t_start, dt, first, last, tl, ddmc);
   });
+  mesh->last_grid = ctx->grid_max;
   if (ev_stop) (void)hipEventRecord(ev_stop, ctx->stream);
   if (st != JB_COMPLETE) return st;
   JB_HIP(hipGetLastError());
@@ -1837,6 +1847,7 @@ extern "C" jb_status jb_verify_swarm(jb_context *ctx, jb_mesh *mesh, const jb_sw
 extern "C" const char *jb_last_transport_variant(const jb_mesh *mesh) {
   return mesh ? mesh->last_variant : "";
 }
+extern "C" int jb_last_transport_grid(const jb_mesh *mesh) { return mesh ? mesh->last_grid : 0; }
 extern "C" int jb_mesh_exact_geometry(const jb_mesh *mesh) { return mesh && mesh->exact_geom; }
 extern "C" int jb_mesh_ddmc_classes(const jb_mesh *mesh) { return mesh ? mesh->nclass_host : 0; }
 extern "C" jb_status jb_set_arithmetic(jb_context *ctx, int mode) {
