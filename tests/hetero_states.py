@@ -19,7 +19,7 @@ from jaybenne_amd import mcblock
 from test_gpu_parity import C5_LEVEL2, CASES as PARITY_CASES, SMR3D, SMR_OVERRIDES
 
 PATTERNS = ("smooth", "smooth_dense", "palette2", "palette3", "stripes3", "stripes2", "islands", "threshold",
-            "hot_spots", "hot_islands")
+            "hot_spots", "hot_islands", "smooth_hot_fine")
 PALETTES = {"palette2": (1.0, 1.5), "palette3": (1.0, 1.25, 1.5)}
 ISLAND_A = 2.0
 
@@ -82,6 +82,16 @@ def _hot(X, Y, Z, ndim):
         f = f * np.sin(13.0 * Y + 0.5 + 2.0 * X)
     if ndim >= 3:
         f = f * np.sin(6.0 * Z - 0.9 + 3.0 * Y)
+    return 1.0 + 0.5 * f
+
+
+def _hot_fine(X, Y, Z, ndim):
+    # the wave numbers of smooth_dense: a per-event temperature gather is felt over a handful of events
+    f = np.sin(61.0 * X + 0.3)
+    if ndim >= 2:
+        f = f * np.cos(47.0 * Y - 0.2 + 13.0 * X)
+    if ndim >= 3:
+        f = f * np.cos(37.0 * Z + 1.1 + 17.0 * Y)
     return 1.0 + 0.5 * f
 
 
@@ -157,6 +167,10 @@ def rho_factor(mesh, pkg, pattern, b, shift=(0, 0, 0), salt=0, tau_ddmc=None):
         return f, (_hot(X, Y, Z, nd) if pattern == "hot_islands" else one)
     if pattern == "hot_spots":
         return one, _hot(X, Y, Z, nd)
+    if pattern == "smooth_hot_fine":
+        # BOTH factors vary in every cell: rho as "smooth", sie by short waves -- for the opacity models that read
+        # the temperature at every event (tests/freq_cases.py); the long waves of _hot change too little there
+        return 1.0 + 0.5 * _smooth(X, Y, Z, nd), _hot_fine(X, Y, Z, nd)
     raise ValueError(pattern)
 
 
@@ -266,9 +280,9 @@ def regime_crossings(ddmc, before, after):
     return float(np.mean(~a & b)), float(np.mean(a & ~b))
 
 
-def differing_photons(A, B):
+def differing_photons(A, B, skip=()):
     """Share of the photons of oracle run A (found by creation id) that are missing from run B or differ from
-    their twin there in any attribute."""
+    their twin there in any attribute (but those named in ``skip``)."""
     ia, ib = A.sw["id"][:A.n], B.sw["id"][:B.n]
     oa, ob = np.argsort(ia), np.argsort(ib)
     pos = np.searchsorted(ib[ob], ia[oa])
@@ -276,6 +290,8 @@ def differing_photons(A, B):
     diff = ~found
     qa, qb = oa[found], ob[pos[found]]
     for k in A.sw:
+        if k in skip:
+            continue
         diff[found] |= A.sw[k][:A.n][qa] != B.sw[k][:B.n][qb]
     return float(diff.mean())
 

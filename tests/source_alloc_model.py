@@ -37,11 +37,15 @@ def erad_thermal(sie, cv, sb, c, dv):
     return ((4.0 * sb / c) * (t2 * t2)) * dv
 
 
-def erad_emission(rho, sie, fleck, cv, sb, kappa, dv, dt):
-    """((fleck j) dv) dt with the gray emissivity j = (rho kappa) ((4 sb) (T^2 T^2)) (sourcing.cpp:95-96)."""
+def erad_emission(rho, sie, fleck, cv, sb, kappa, dv, dt, ep_E=None):
+    """((fleck j) dv) dt with the gray emissivity j = (rho kappa) ((4 sb) (T^2 T^2)) (sourcing.cpp:95-96) or, with
+    ``ep_E`` (the EPBremss coefficient E in code units, include/jaybenne_amd.h), j = (E (rho rho)) sqrt(T)."""
     t = temperature(sie, cv)
-    t2 = t * t
-    j = (rho * kappa) * ((4.0 * sb) * (t2 * t2))
+    if ep_E is not None:
+        j = (ep_E * (rho * rho)) * np.sqrt(t)
+    else:
+        t2 = t * t
+        j = (rho * kappa) * ((4.0 * sb) * (t2 * t2))
     return ((fleck * j) * dv) * dt
 
 
@@ -142,7 +146,7 @@ class Call:
 def source_call(mesh, rho, sie, fleck, par, source_type, dt, n_target, epoch, blocks=None):
     """``rho``, ``sie``, ``fleck``: [len(blocks), nk, nj, ni] with ghosts (fleck may be None for the thermal source);
     ``blocks``: the global ids of their rows (default: the whole mesh, which a call needs for E_tot -- a partial list
-    gives that rank's block sums only and stops there); ``par``: dict(cv, sb, c, kappa, seed)."""
+    gives that rank's block sums only and stops there); ``par``: dict(cv, sb, c, kappa, seed) and, for EPBremss, ep_E."""
     whole = blocks is None
     blocks = list(range(mesh.nblocks)) if whole else [int(b) for b in blocks]
     check_target(n_target, mesh.ncell)
@@ -154,7 +158,8 @@ def source_call(mesh, rho, sie, fleck, par, source_type, dt, n_target, epoch, bl
         if source_type == THERMAL:
             e = erad_thermal(sie[row][sl], par["cv"], par["sb"], par["c"], dv)
         else:
-            e = erad_emission(rho[row][sl], sie[row][sl], fleck[row][sl], par["cv"], par["sb"], par["kappa"], dv, dt)
+            e = erad_emission(rho[row][sl], sie[row][sl], fleck[row][sl], par["cv"], par["sb"], par["kappa"], dv, dt,
+                              par.get("ep_E"))
         out.erad[b] = e
         out.e_block[b] = block_sum(e)
     if not whole:

@@ -71,8 +71,13 @@ def _driver(deck, ov, device, state=BothState(), **kw):
 
 
 def _par(drv):
+    from jaybenne_amd import mcblock
     o = drv.mcb.opacity
-    return dict(cv=drv.mcb.eos.cv, sb=o.sb, c=o.c, kappa=o.kappa, seed=drv.pin.GetOrAddInteger("jaybenne", "seed", 123))
+    par = dict(cv=drv.mcb.eos.cv, sb=o.sb, c=o.c, kappa=o.kappa, seed=drv.pin.GetOrAddInteger("jaybenne", "seed", 123))
+    if o.model == mcblock.OPAC_EPBREMSS:     # (the library's coefficients are the oracle's: test_gpu_parity)
+        from oracle import orc
+        par["ep_E"] = orc.model_coefficients(o.time_scale, o.mass_scale, o.length_scale, o.temperature_scale)["ep_E"]
+    return par
 
 
 def _host(md, name):
@@ -157,6 +162,31 @@ def test_count_equals_the_model(gpu_device, geom, n, source):
     _lib.check(md.lib.jb_source_photons_count(md.pkg.ctx, md.handle, int(st), dt, 1, 5, nper2.ctypes.data,
                                               md.prefix.data_ptr()))
     _compare(drv, call, e_local, e_total, nper2)
+
+
+@pytest.mark.parametrize("source", ["thermal", "emission"])
+def test_count_equals_the_model_under_epbremss(gpu_device, source):
+    """k_salloc_energy's emission branch forms fleck * opac_emissivity * dv * dt: with EPBremss the emissivity is
+    (E (rho rho)) sqrt(T).  The 3-D two-level row of tests/freq_cases.py (rho and sie different in every cell, the
+    Fleck factor from the frequency-integrated emissivity), under source_allocation = energy."""
+    import freq_cases as fc
+    from jaybenne_amd import _lib, jaybenne as jb, mcblock
+    case = fc.BY_ID["F3S-hybrid"]
+    ov = fc.overrides(case, **{ALLOC: "energy"})
+    drv = _driver(case.deck, ov, gpu_device, state=hs.state_for(case.deck, ov, fc.PATTERN), capacity_factor=fc.CAPACITY_FACTOR)
+    md = drv.md
+    assert md.source_allocation == "energy" and md.lib.jb_get_source_allocation(md.pkg.ctx) == _lib.ALLOC_ENERGY
+    assert drv.mcb.opacity.model == mcblock.OPAC_EPBREMSS and _par(drv)["ep_E"] > 0.0 and _par(drv)["kappa"] == 0.0
+    st = jb.SourceType[source]
+    dt = drv.dt if source == "emission" else 0.0
+    jb.UpdateDerivedTransportFields(md, drv.dt)
+    e_local, e_total, nper, staged = _two_phase(md, st, dt, 5)
+    call = _model(drv, st, dt, 5)
+    _compare(drv, call, e_local, e_total, nper, staged)
+    n_all = np.concatenate([call.n[b].reshape(-1) for b in range(drv.mesh.nblocks)])
+    assert (n_all >= 2).any() and (n_all == 0).any() and abs(int(n_all.sum()) - case.photons) <= n_all.size
+    f = _host(md, "fleck")[drv.mesh.interior()]
+    assert len(np.unique(f)) > 0.4 * f.size              # a Fleck factor of its own in (nearly) every cell
 
 
 def test_view_with_a_halo_copy(gpu_device):

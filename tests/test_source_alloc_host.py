@@ -201,27 +201,67 @@ def test_unbiasedness_is_exact():
 def test_counts_add_up_to_the_target():
     for n_target, st in ((20000, sam.THERMAL), (777, sam.EMISSION), (3, sam.THERMAL)):
         mesh, par, ic, call = _mesh_call(n_target, st)
-        erad = np.concatenate([call.erad[b].reshape(-1) for b in range(mesh.nblocks)])
-        n = np.concatenate([call.n[b].reshape(-1) for b in range(mesh.nblocks)])
-        ew = np.concatenate([call.ew[b].reshape(-1) for b in range(mesh.nblocks)])
-        nu = erad * call.scale
-        sourcing = int((erad > 0.0).sum())
-        assert sourcing == erad.size
-        # sum nu = N to rounding: each nu carries one rounding of the product and scale one of the quotient, E_tot
-        # the roundings of its two-stage sum
-        assert abs(math.fsum(nu) - n_target) <= n_target * U * (mesh.ncell + mesh.nblocks + 4)
-        assert abs(int(n.sum()) - n_target) <= sourcing
-        assert np.all(np.abs(n - nu) < 1.0) and sum(call.nper.values()) == int(n.sum())
-        # every cell with f >= 1 carries its energy exactly (to the neighbouring double)
-        full = np.floor(nu) >= 1.0
-        assert np.all(np.abs(n[full] * ew[full] - erad[full]) <= np.spacing(erad[full]))
-        for b in range(mesh.nblocks):
-            cnt = np.rint(call.n[b].reshape(-1)).astype(np.int64)
-            assert np.array_equal(call.prefix[b], np.cumsum(cnt) - cnt) and call.nper[b] == cnt.sum()
-            for p in (0, call.nper[b] // 2, call.nper[b] - 1):
-                if call.nper[b]:
-                    cell = sam.cell_of(call.prefix[b], p)
-                    assert call.prefix[b][cell] <= p < call.prefix[b][cell] + cnt[cell]
+        _counts_add_up(mesh, call, n_target)
+
+
+def test_epbremss_emission_on_the_3d_two_level_row():
+    """The emission source of tests/freq_cases.py's F3S-hybrid row (EPBremss, rho and sie different in every cell, dv
+    different by level) under source_allocation = energy: the model's emissivity (E (rho rho)) sqrt(T) is the
+    oracle's ``opac_emissivity`` bit for bit, erad = ((fleck j) dv) dt with the oracle's Fleck factor, and the counts
+    add up as they do for the gray form."""
+    import freq_cases as fc
+    from oracle import orc
+    case = fc.BY_ID["F3S-hybrid"]
+    pin, O, mesh, mcb = fc.oracle_of(case, **{KEY: "energy"})
+    assert mcblock.source_allocation_of(pin) == "energy" and mcb.opacity.model == mcblock.OPAC_EPBREMSS
+    assert mesh.ndim == 3 and set(mesh.blk_level) == {0, 1}
+    par_o = fc.model_params(pin, mcb)
+    dt = pin.GetReal("jaybenne", "dt")
+    O.UpdateDerivedTransportFields(dt)
+    par = dict(cv=mcb.eos.cv, sb=mcb.opacity.sb, c=mcb.opacity.c, kappa=mcb.opacity.kappa, ep_E=par_o["ep_E"],
+               seed=pin.GetOrAddInteger("jaybenne", "seed", 123))
+    assert par["kappa"] == 0.0 and par["ep_E"] > 0.0
+    call = sam.source_call(mesh, O.fields["rho"], O.fields["sie"], O.fields["fleck"], par, sam.EMISSION, dt, case.photons, 1)
+    sl = mesh.interior()[1:]
+    orc.set_math_mode(orc.MATH_PORTABLE)
+    for b in range(mesh.nblocks):
+        rho, fleck = O.fields["rho"][b][sl], O.fields["fleck"][b][sl]
+        temp = sam.temperature(O.fields["sie"][b][sl], par["cv"])
+        j = orc.model_eval(par_o, 1, rho, temp, np.ones_like(rho)).reshape(rho.shape)
+        dv = (mesh.blk_dx[b, 0] * mesh.blk_dx[b, 1]) * mesh.blk_dx[b, 2]
+        assert np.array_equal(call.erad[b], ((fleck * j) * dv) * dt), b
+    f = O.fields["fleck"][mesh.interior()]
+    assert len(np.unique(f)) > 0.4 * f.size and 0.0 < f.min() and f.max() <= 1.0
+    n = _counts_add_up(mesh, call, case.photons)
+    print(f"EPBremss emission on {case.id}: E_tot {call.e_total:.6e}, {int(n.sum())} photons for a target of {case.photons}, "
+          f"{int((n == 0).sum())} cells without one, {int((n >= 2).sum())} with several")
+    assert (n >= 2).any() and (n == 0).any()
+
+
+def _counts_add_up(mesh, call, n_target):
+    """The assertions on one whole call: sum nu = N, the counts, the carried energy, the prefix."""
+    erad = np.concatenate([call.erad[b].reshape(-1) for b in range(mesh.nblocks)])
+    n = np.concatenate([call.n[b].reshape(-1) for b in range(mesh.nblocks)])
+    ew = np.concatenate([call.ew[b].reshape(-1) for b in range(mesh.nblocks)])
+    nu = erad * call.scale
+    sourcing = int((erad > 0.0).sum())
+    assert sourcing == erad.size
+    # sum nu = N to rounding: each nu carries one rounding of the product and scale one of the quotient, E_tot
+    # the roundings of its two-stage sum
+    assert abs(math.fsum(nu) - n_target) <= n_target * U * (mesh.ncell + mesh.nblocks + 4)
+    assert abs(int(n.sum()) - n_target) <= sourcing
+    assert np.all(np.abs(n - nu) < 1.0) and sum(call.nper.values()) == int(n.sum())
+    # every cell with f >= 1 carries its energy exactly (to the neighbouring double)
+    full = np.floor(nu) >= 1.0
+    assert np.all(np.abs(n[full] * ew[full] - erad[full]) <= np.spacing(erad[full]))
+    for b in range(mesh.nblocks):
+        cnt = np.rint(call.n[b].reshape(-1)).astype(np.int64)
+        assert np.array_equal(call.prefix[b], np.cumsum(cnt) - cnt) and call.nper[b] == cnt.sum()
+        for p in (0, call.nper[b] // 2, call.nper[b] - 1):
+            if call.nper[b]:
+                cell = sam.cell_of(call.prefix[b], p)
+                assert call.prefix[b][cell] <= p < call.prefix[b][cell] + cnt[cell]
+    return n
 
 
 def test_nothing_to_source_and_bad_totals():
