@@ -2,7 +2,7 @@
 // what the reference's src/mcblock does around the jaybenne package, on one GPU, with no Python
 // and no PyTorch in the process.
 //
-//   mcblock_amd -i <deck> [block/key=value ...] [--tolerance X] [--dump file] [--ledger file] [--moments file]
+//   mcblock_amd -i <deck> [block/key=value ...] [--tolerance X] [--dump file] [--ledger file] [--moments file] [--comb-history file]
 //
 // Input deck syntax and the trailing overrides are Parthenon's (reference inputs/*.in; the
 // regression harness tst/regression_test.py:85-145 rewrites decks the same way).  It sets up the
@@ -187,7 +187,7 @@ static uint64_t Morton(const int l[3], int bits) {
 
 int main(int argc, char **argv) {
   try {
-    std::string deck, dump, ledger_path, moments_path;
+    std::string deck, dump, ledger_path, moments_path, comb_path;
     double tolerance = -1.0;
     std::vector<std::string> overrides;
     for (int a = 1; a < argc; ++a) {
@@ -197,10 +197,11 @@ int main(int argc, char **argv) {
       else if (s == "--dump" && a + 1 < argc) dump = argv[++a];
       else if (s == "--ledger" && a + 1 < argc) ledger_path = argv[++a];
       else if (s == "--moments" && a + 1 < argc) moments_path = argv[++a];
+      else if (s == "--comb-history" && a + 1 < argc) comb_path = argv[++a];
       else overrides.push_back(s);
     }
     if (deck.empty()) {
-      std::fprintf(stderr, "usage: mcblock_amd -i deck [block/key=value ...] [--tolerance X] [--dump file] [--ledger file] [--moments file]\n");
+      std::fprintf(stderr, "usage: mcblock_amd -i deck [block/key=value ...] [--tolerance X] [--dump file] [--ledger file] [--moments file] [--comb-history file]\n");
       return 2;
     }
     ParameterInput pin;
@@ -582,6 +583,13 @@ int main(int argc, char **argv) {
     // ceil(census_comb_trigger * census_per_cell_max) photons comes out with census_per_cell_max; 0 = off)
     md.comb_target = pin.GetOrAddInteger("jaybenne_amd", "census_per_cell_max", 0);
     md.comb_trigger = jb::CombTrigger(md.comb_target, pin.GetOrAddReal("jaybenne_amd", "census_comb_trigger", 2.0));
+    // (as the Python driver: the global census comb -- the whole mesh is held near census_total_target photons of
+    // equal weight; a cell off its share by more than the factor census_total_band is combed, and grows to at most
+    // census_split_max times its count; 0 = off; not together with census_per_cell_max)
+    md.census_total_target = pin.GetOrAddInteger("jaybenne_amd", "census_total_target", 0);
+    md.census_total_band = pin.GetOrAddReal("jaybenne_amd", "census_total_band", 2.0);
+    md.census_split_max = pin.GetOrAddInteger("jaybenne_amd", "census_split_max", 64);
+    jb::CheckCensusTotal(md.census_total_target, md.census_total_band, md.census_split_max, md.comb_target);
     // (as the Python driver: the order within a cell behind a sort -- any, or id: the canonical order)
     jb::SetCellOrder(&md, jb::CellOrderOf(pin.GetOrAddString("jaybenne_amd", "cell_order", "any")));
     // (as the Python driver: deposition = exact -- energy_delta and the tally as one rounding of the exact sum;
@@ -624,6 +632,10 @@ int main(int argc, char **argv) {
     std::FILE *moments_file = nullptr;
     if (!moments_path.empty() && !(moments_file = std::fopen(moments_path.c_str(), "w")))
       throw std::runtime_error("cannot write " + moments_path);
+    // --comb-history FILE: one JSON line per cycle whose census comb changed the swarm
+    std::FILE *comb_file = nullptr;
+    if (!comb_path.empty() && !(comb_file = std::fopen(comb_path.c_str(), "w")))
+      throw std::runtime_error("cannot write " + comb_path);
     std::printf("problem %s: %d-D, %d meshblocks, %d level(s), %lld photons\n", problem_id.c_str(), ndim,
                 nb, max_level + 1, (long long)md.swarm.n);
 
@@ -658,9 +670,11 @@ int main(int argc, char **argv) {
         std::printf(" leak=[%.6e, %.6e, %.6e, %.6e, %.6e, %.6e] residual=%.3e", l.e_escaped[0], l.e_escaped[1],
                     l.e_escaped[2], l.e_escaped[3], l.e_escaped[4], l.e_escaped[5], l.residual);
       }
-      if (!md.comb_history.empty() && md.comb_history.back().cycle == (int64_t)md.cycle)
+      if (!md.comb_history.empty() && md.comb_history.back().cycle == (int64_t)md.cycle) {
         std::printf(" combed=%lld new_ids=%lld", (long long)md.comb_history.back().cells_combed,
                     (long long)md.comb_history.back().n_new_ids);
+        if (comb_file) std::fprintf(comb_file, "%s\n", jb::CombJson(md.comb_history.back()).c_str());
+      }
       if (moments_file) {
         jb_moments_report rep{};
         const std::vector<double> mom = jb::EvaluateRadiationMoments(&md, &rep);
@@ -672,6 +686,7 @@ int main(int argc, char **argv) {
     }
     if (ledger_file) std::fclose(ledger_file);
     if (moments_file) std::fclose(moments_file);
+    if (comb_file) std::fclose(comb_file);
     if (jb::LedgerEnabled(&md)) {   // totals by face
       static const char *const kFaces[6] = {"ix1", "ox1", "ix2", "ox2", "ix3", "ox3"};
       std::printf("leakage by face:");

@@ -110,6 +110,10 @@ struct CombRecord {
   uint64_t id_base;
   int64_t cells_combed, max_per_cell;
   double e_before, e_after;
+  // a cycle of the global comb (CombCensusGlobal; the Python host's mode = "global") fills these too
+  bool global = false;
+  int64_t cells_thinned = 0, cells_split = 0, max_target = 0;
+  double w_total = 0.0, scale = 0.0;
 };
 inline double LedgerResidual(const jb_energy_ledger &l, double e_start) {
   const double lhs = e_start + l.e_sourced;
@@ -128,8 +132,8 @@ class MeshData {
  public:
   MeshData(std::shared_ptr<StateDescriptor> pkg, const jb_mesh_view &view, int32_t *prefix_dev,
            std::function<void(jb_swarm_view &, int64_t)> reserve)
-      : pkg_(std::move(pkg)), nblocks_(view.nblocks), prefix_dev_(prefix_dev),
-        reserve_(std::move(reserve)) {
+      : pkg_(std::move(pkg)), nblocks_(view.nblocks), nblocks_total_(view.nblocks_total),
+        gid_(view.gid, view.gid + view.nblocks), prefix_dev_(prefix_dev), reserve_(std::move(reserve)) {
     Check(jb_mesh_create(pkg_->ctx(), &view, &mesh_));
   }
   ~MeshData() { jb_mesh_destroy(mesh_); }
@@ -140,6 +144,8 @@ class MeshData {
   jb_context *ctx() const { return pkg_->ctx(); }
   jb_mesh *mesh() const { return mesh_; }
   int nblocks() const { return nblocks_; }
+  int nblocks_total() const { return nblocks_total_; }
+  const std::vector<int32_t> &gid() const { return gid_; }   // global id of each resident block
   int32_t *prefix_dev() const { return prefix_dev_; }
   void Reserve(int64_t n) {
     if (n > swarm.capacity) reserve_(swarm, n);
@@ -176,6 +182,10 @@ class MeshData {
   // comb_trigger photons comes out with comb_target; 0 = off (the reference: no population control)
   int64_t comb_target = 0, comb_trigger = 0;
   std::vector<CombRecord> comb_history;   // one record per cycle whose comb changed the swarm
+  // global census comb (CombCensusGlobal; jaybenne_amd.h: jb_comb_census_weigh): the whole mesh is held near
+  // census_total_target photons of equal weight; 0 = off.  Not together with comb_target.
+  int64_t census_total_target = 0, census_split_max = 64;
+  double census_total_band = 2.0;
   // boundary source (SetBoundarySource; jaybenne_amd.h: jb_source_boundary_count): N_b photons per cycle over all
   // source faces of the WHOLE mesh, and the number of source face cells of the whole mesh (SetBoundarySource sets it
   // for a rank that holds the whole mesh; a host with several ranks stores the sum of jb_boundary_face_cells)
@@ -193,7 +203,8 @@ class MeshData {
  private:
   std::shared_ptr<StateDescriptor> pkg_;
   jb_mesh *mesh_ = nullptr;
-  int nblocks_;
+  int nblocks_, nblocks_total_;
+  std::vector<int32_t> gid_;
   int32_t *prefix_dev_;
   std::function<void(jb_swarm_view &, int64_t)> reserve_;
 };
@@ -765,11 +776,79 @@ inline bool CombCensus(MeshData *md) {
   }
   return plan.sorted != 0;
 }
+// The ranges of the deck keys <jaybenne_amd> census_total_target, census_total_band and census_split_max (every host
+// checks them this way), and that the global comb is not asked for together with the per-cell comb.
+inline void CheckCensusTotal(int64_t target, double band, int64_t split_max, int64_t per_cell_max = 0) {
+  if (target < 0 || target >= ((int64_t)1 << 31)) throw std::invalid_argument("census_total_target must be in [0, 2^31)");
+  if (!(band >= 1.0) || !std::isfinite(band)) throw std::invalid_argument("census_total_band must be a finite number >= 1");
+  if (split_max < 1) throw std::invalid_argument("census_split_max must be >= 1");
+  if (target > 0 && per_cell_max > 0)
+    throw std::invalid_argument("census_total_target and census_per_cell_max: one comb at a time -- the global comb "
+                                "deals the cells their shares itself");
+}
+// Census population control for the whole mesh at the end of a cycle, single process (not in the reference's task
+// list): the swarm is held near md->census_total_target photons of equal weight -- the target is dealt to the cells
+// in proportion to the census energy they hold; a cell off its share by more than the factor census_total_band is
+// thinned or split to it (at most to census_split_max times its count) and keeps its energy (jaybenne_amd.h:
+// jb_comb_census_weigh / _plan_global / _apply).  The mesh is wholly resident and owned here: the block sums are
+// ordered by global block id and added by jb_source_energy_total, as every host adds them.  Returns true when the
+// weigh sorted the swarm.
+inline bool CombCensusGlobal(MeshData *md) {
+  const int64_t N = md->census_total_target;
+  if (N <= 0) return false;
+  CheckCensusTotal(N, md->census_total_band, md->census_split_max, md->comb_target);
+  if (md->nblocks() != md->nblocks_total())
+    throw std::invalid_argument("CombCensusGlobal: this host adds the block sums of one process; the mesh must be wholly resident");
+  const int64_t n = md->swarm.n, S = md->census_split_max;
+  const int64_t n_room = n + N < S * n ? n + N : S * n;   // (n_after <= n + N: every combed cell had a photon)
+  md->Reserve(n_room);
+  jb_comb_global_plan plan{};
+  std::vector<double> e_local((size_t)md->nblocks()), e_gid((size_t)md->nblocks_total(), 0.0);
+  Check(jb_comb_census_weigh(md->ctx(), md->mesh(), &md->swarm, n_room, e_local.data(), &plan));
+  for (int b = 0; b < md->nblocks(); ++b) e_gid[(size_t)md->gid()[(size_t)b]] = e_local[(size_t)b];
+  const double w_total = jb_source_energy_total(e_gid.data(), md->nblocks_total());
+  if (w_total > 0.0 && std::isfinite(w_total))
+    Check(jb_comb_census_plan_global(md->ctx(), md->mesh(), &md->swarm, w_total, N, md->census_total_band, S,
+                                     (uint32_t)md->cycle, &plan));
+  if (plan.cells_thinned + plan.cells_split > 0) {
+    jb_comb_report rep{};
+    Check(jb_comb_census_apply(md->ctx(), md->mesh(), &md->swarm, md->next_id, &rep));
+    CombRecord r{(int64_t)md->cycle, plan.n_before, rep.n_after, rep.n_new_ids, md->next_id,
+                 plan.cells_thinned + plan.cells_split, plan.max_per_cell, plan.e_before, rep.e_after};
+    r.global = true;
+    r.cells_thinned = plan.cells_thinned;
+    r.cells_split = plan.cells_split;
+    r.max_target = plan.max_target;
+    r.w_total = w_total;
+    r.scale = (double)N / w_total;
+    md->comb_history.push_back(r);
+    md->next_id += (uint64_t)rep.n_new_ids;
+  }
+  return plan.sorted != 0;
+}
+// One line of JSON per combed cycle (the keys of the Python host's md.comb_history, %.17g: both hosts print the same
+// bits); the global comb's keys only for its records.
+inline std::string CombJson(const CombRecord &r) {
+  char buf[1024];
+  int len = std::snprintf(buf, sizeof buf,
+                          "{\"cycle\": %lld, \"n_before\": %lld, \"n_after\": %lld, \"n_new_ids\": %lld, \"id_base\": %llu, "
+                          "\"cells_combed\": %lld, \"max_per_cell\": %lld, \"e_before\": %.17g, \"e_after\": %.17g",
+                          (long long)r.cycle, (long long)r.n_before, (long long)r.n_after, (long long)r.n_new_ids,
+                          (unsigned long long)r.id_base, (long long)r.cells_combed, (long long)r.max_per_cell, r.e_before,
+                          r.e_after);
+  if (r.global)
+    len += std::snprintf(buf + len, sizeof buf - (size_t)len,
+                         ", \"mode\": \"global\", \"cells_thinned\": %lld, \"cells_split\": %lld, \"max_target\": %lld, "
+                         "\"w_total\": %.17g, \"scale\": %.17g",
+                         (long long)r.cells_thinned, (long long)r.cells_split, (long long)r.max_target, r.w_total, r.scale);
+  return std::string(buf) + "}";
+}
 // the end of a cycle: the comb where it is on, then DefragParticles' schedule.  A cycle whose comb sorted the
 // swarm counts as a sort: the k-th-cycle counter starts over; the library's schedule has started over inside
 // the plan and is still called (it reads the cycle's kernel times and, one cycle behind a sort, never sorts).
 inline void CombAfterStep(MeshData *md, int64_t events) {
-  if (CombCensus(md) && md->defrag_interval >= 0) {
+  const bool sorted = md->census_total_target > 0 ? CombCensusGlobal(md) : CombCensus(md);
+  if (sorted && md->defrag_interval >= 0) {
     md->steps_since_defrag = 0;
     return;
   }

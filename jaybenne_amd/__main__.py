@@ -63,6 +63,19 @@ def moments_json(cycle: int, t: float, report: dict, integ: dict) -> str:
             f'"eddington": {lst(integ["eddington"])}' + "}")
 
 
+def comb_json(rec: dict) -> str:
+    """One combed cycle's line of ``--comb-history FILE`` (examples/mcblock_amd writes the same characters: %.17g
+    restores a float's bits); the global comb's keys only for its records."""
+    g = lambda x: "%.17g" % x                           # noqa: E731
+    s = (f'"cycle": {int(rec["cycle"])}, "n_before": {rec["n_before"]}, "n_after": {rec["n_after"]}, '
+         f'"n_new_ids": {rec["n_new_ids"]}, "id_base": {rec["id_base"]}, "cells_combed": {rec["cells_combed"]}, '
+         f'"max_per_cell": {rec["max_per_cell"]}, "e_before": {g(rec["e_before"])}, "e_after": {g(rec["e_after"])}')
+    if rec.get("mode") == "global":
+        s += (f', "mode": "global", "cells_thinned": {rec["cells_thinned"]}, "cells_split": {rec["cells_split"]}, '
+              f'"max_target": {rec["max_target"]}, "w_total": {g(rec["w_total"])}, "scale": {g(rec["scale"])}')
+    return "{" + s + "}"
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m jaybenne_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -87,6 +100,9 @@ def main(argv=None) -> int:
                     help="after every cycle one JSON line to FILE: the report of EvaluateRadiationMoments and the "
                          "domain integrals of count, energy, flux and second-moment tensor, with the Eddington "
                          "factors (the deck key <jaybenne_amd> moments = true: to moments.jsonl)")
+    ap.add_argument("--comb-history", default=None, metavar="FILE",
+                    help="one JSON line to FILE per cycle whose census comb (census_per_cell_max or "
+                         "census_total_target) changed the swarm")
     ap.add_argument("overrides", nargs="*", help="block/key=value")
     args = ap.parse_args(argv)
 
@@ -109,6 +125,7 @@ def main(argv=None) -> int:
     ledger_file = open(args.ledger, "w") if args.ledger else None
     moments_path = args.moments or ("moments.jsonl" if pin.GetOrAddBoolean("jaybenne_amd", "moments", False) else None)
     moments_file = open(moments_path, "w") if moments_path else None
+    comb_file = open(args.comb_history, "w") if args.comb_history else None
     print(f"problem {drv.mcb.problem_id}: {drv.mesh.ndim}-D, {drv.mesh.nblocks} meshblocks, "
           f"levels {sorted(set(drv.mesh.blk_level.tolist()))}, {drv.md.n} photons")
     t0 = time.perf_counter()
@@ -132,6 +149,8 @@ def main(argv=None) -> int:
                 line += " leak=[" + ", ".join(f"{e:.6e}" for e in led["e_escaped"]) + f"] residual={led['residual']:.3e}"
             if drv.md.comb_history and drv.md.comb_history[-1]["cycle"] == drv.md.cycle:
                 line += f" combed={drv.md.comb_history[-1]['cells_combed']} new_ids={drv.md.comb_history[-1]['n_new_ids']}"
+                if comb_file is not None:
+                    comb_file.write(comb_json(drv.md.comb_history[-1]) + "\n")
             if moments_file is not None:
                 fields, rep = drv.jb.EvaluateRadiationMoments(drv.md)
                 integ = moments_integrals(fields.cpu().numpy(), np.asarray(drv.mesh.blk_dx)[drv.md.resident_gids],
@@ -148,6 +167,8 @@ def main(argv=None) -> int:
     print(f"walltime used = {time.perf_counter() - t0:.2f} s")
     if moments_file is not None:
         moments_file.close()
+    if comb_file is not None:
+        comb_file.close()
     if ledger_file is not None:
         ledger_file.close()
         import math

@@ -205,6 +205,13 @@ class CombReport(C.Structure):
     _fields_ = [("n_after", C.c_int64), ("n_new_ids", C.c_int64), ("e_after", C.c_double)]
 
 
+# jb_comb_global_plan (include/jaybenne_amd.h): the global census comb
+class CombGlobalPlan(C.Structure):
+    _fields_ = [("n_before", C.c_int64), ("n_after", C.c_int64), ("n_new_ids", C.c_int64),
+                ("cells_thinned", C.c_int64), ("cells_split", C.c_int64), ("max_per_cell", C.c_int64),
+                ("max_target", C.c_int64), ("sorted", C.c_int64), ("e_before", C.c_double)]
+
+
 # jb_moments_report (include/jaybenne_amd.h): radiation moments; MOMENT_NAMES in the order of the enum JB_MOM_*
 JB_MOMENTS = 12
 MOMENT_NAMES = ("n", "e", "w2", "fx", "fy", "fz", "qxx", "qxy", "qxz", "qyy", "qyz", "qzz")
@@ -283,6 +290,10 @@ PROTOTYPES = {
     "jb_release_scratch": (_int, [_vp]),
     "jb_comb_census_plan": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, _i64, C.c_uint32, C.POINTER(CombPlan)]),
     "jb_comb_census_apply": (_int, [_vp, _vp, C.POINTER(SwarmView), C.c_uint64, C.POINTER(CombReport)]),
+    "jb_comb_census_weigh": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, _vp, C.POINTER(CombGlobalPlan)]),
+    "jb_gcomb_kernel_launches": (_i64, [_vp]),
+    "jb_comb_census_plan_global": (_int, [_vp, _vp, C.POINTER(SwarmView), C.c_double, _i64, C.c_double, _i64,
+                                          C.c_uint32, C.POINTER(CombGlobalPlan)]),
     "jb_moments_words": (_i64, [_vp]),
     "jb_evaluate_radiation_moments": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, C.POINTER(MomentsReport)]),
     "jb_evaluate_radiation_moments_host": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, C.POINTER(MomentsReport)]),

@@ -25,6 +25,7 @@
 #include "jb_kernel_imc.hpp"
 #include "jb_kernel_ledger.hpp"
 #include "jb_kernel_comb.hpp"
+#include "jb_kernel_gcomb.hpp"
 #include "jb_kernel_order.hpp"
 #include "jb_kernel_bsource.hpp"
 #include "jb_kernel_deposit.hpp"
@@ -107,7 +108,23 @@ struct jb_context {
     unsigned T = 0, K = 0;
     int ends_shift = 0;                       // the cells' ends are the histogram array from this entry on
     unsigned long long gen = 0;
+    // a plan of the global comb (jb_comb_census_plan_global): apply runs k_gcomb_pack with the weigh's n_room
+    bool global = false;
+    long long n_room = 0;
   } comb;
+  // jb_comb_census_weigh -> jb_comb_census_plan_global: order, ends and running weights lie in scratch_d
+  struct {
+    bool valid = false;
+    const jb_mesh *mesh = nullptr;
+    const double *x = nullptr;
+    long long n = 0, n_room = 0;
+    int ends_shift = 0;
+    int64_t sorted = 0;
+    double e_before = 0.0;
+    unsigned long long gen = 0;
+  } weigh;
+  long long gcomb_launches = 0;               // kernels of jb_kernel_gcomb.hpp launched so far (jb_gcomb_kernel_launches)
+  DevBuf gcomb_eblock;                        // jb_comb_census_weigh: the block sums (one double per resident block)
   // jb_radiation_step_ranks: the hand-off record buffers (JB_RECORD_WORDS words per record) and the buffer of
   // the step's first all-gather ([status | counts per global block] of this rank, then every rank's)
   DevBuf step_send, step_recv, step_gather;
@@ -620,7 +637,7 @@ extern "C" jb_status jb_finalize(jb_context *ctx) {
   if (ctx->scratch_d) (void)hipFree(ctx->scratch_d);
   if (ctx->ledger_d) (void)hipFree(ctx->ledger_d);
   for (DevBuf *b : {&ctx->xch, &ctx->step_send, &ctx->step_recv, &ctx->step_gather, &ctx->moments, &ctx->ledger_gather,
-                    &ctx->bs_prefix, &ctx->bs_out})
+                    &ctx->bs_prefix, &ctx->bs_out, &ctx->gcomb_eblock})
     (void)dev_free(*b);
   for (hipEvent_t e : ctx->tev) (void)hipEventDestroy(e);
   for (hipEvent_t e : ctx->sort_ev) if (e) (void)hipEventDestroy(e);
@@ -1862,7 +1879,7 @@ extern "C" int jb_get_arithmetic(const jb_context *ctx) {
 extern "C" jb_status jb_set_cell_order(jb_context *ctx, int mode) {
   if (!ctx || (mode != JB_CELL_ORDER_ANY && mode != JB_CELL_ORDER_BY_ID))
     return fail(JB_ERR_INVALID, "jb_set_cell_order: mode = %d is neither JB_CELL_ORDER_ANY nor JB_CELL_ORDER_BY_ID", mode);
-  if (mode != ctx->cell_order) ctx->comb.valid = false;   // (the comb's arrays lie behind the sort's: a plan made before is none now)
+  if (mode != ctx->cell_order) ctx->comb.valid = ctx->weigh.valid = false;   // (the comb's arrays lie behind the sort's: a plan made before is none now)
   ctx->cell_order = mode;
   return JB_COMPLETE;
 }
@@ -2223,36 +2240,18 @@ static jb_status comb_energy(jb_context *ctx, const DevSwarm &S, long long n, do
   return JB_COMPLETE;
 }
 
-extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, int64_t trigger_T,
-                                         int64_t target_K, uint32_t epoch, jb_comb_plan *out) {
-  JB_RANGE("Jaybenne::CombCensus");
-  if (!ctx || !mesh || !out) return fail(JB_ERR_INVALID, "jb_comb_census_plan: null argument");
-  JB_HIP(hipSetDevice(ctx->device));
-  ctx->comb.valid = false;
-  jb_status st = check_swarm(swarm, "jb_comb_census_plan");
-  if (st != JB_COMPLETE) return st;
-  if (target_K < 1 || target_K > trigger_T)
-    return fail(JB_ERR_INVALID, "jb_comb_census_plan: target_K = %lld outside [1, trigger_T = %lld]", (long long)target_K,
-                (long long)trigger_T);
-  if (trigger_T >= (1ll << 32)) return fail(JB_ERR_INVALID, "jb_comb_census_plan: trigger_T beyond 2^32 - 1");
-  if (epoch >= (1u << 20)) return fail(JB_ERR_INVALID, "jb_comb_census_plan: epoch %u beyond 2^20 - 1", epoch);
-  memset(out, 0, sizeof *out);
-  const long long n = swarm->n;
-  out->n_before = out->n_after = n;
-  if (n == 0) return JB_COMPLETE;
+// Steps shared by jb_comb_census_plan and jb_comb_census_weigh: the swarm into (block, cell) order, the cells' ends
+// (*ends_out) and the running weights c.C.  *unsorted_out: the swarm was not in order (it has been sorted).
+static jb_status comb_order_and_weigh(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, const CellKeys &k,
+                                      const CombLayout &L, const CombScratch &c, unsigned *unsorted_out,
+                                      const unsigned **ends_out, int64_t *sorted) {
   const DevMesh &M = mesh->dm;
-  const CellKeys k = cell_keys(M.nblocks, M.ntot, n);
-  if ((st = check_cell_keys(k, "jb_comb_census_plan")) != JB_COMPLETE) return st;
-  const unsigned nkeys = k.nkeys;
-  const bool by_id = order_by_id(ctx);
-  const CombLayout L = comb_layout(n, k.nbins, by_id);
-  // (all of the scratch first: the sort then finds room, and a failed allocation leaves the swarm as it was)
-  st = ensure_scratch(ctx, L.words, /*slack=*/false);
-  if (st != JB_COMPLETE) return st;
-  const CombScratch c = comb_scratch(ctx, L);
   const DevSwarm S = dev_swarm(swarm);
-  const unsigned T = (unsigned)trigger_T, K = (unsigned)target_K;
-  const int gn = grid_for(ctx, n), gc = comb_parts((long long)nkeys), nt = L.ntiles;
+  const long long n = swarm->n;
+  const unsigned nkeys = k.nkeys;
+  const bool by_id = L.sort.by_id;
+  const int gn = grid_for(ctx, n), nt = L.ntiles;
+  jb_status st;
   // In key order already (behind a DefragParticles, or a comb, that nothing has moved since)?  Then the sort's
   // move is left out -- and the order within a cell, which the move leaves to its atomics, stays the caller's:
   // the same sorted swarm then gives the same bits.
@@ -2281,7 +2280,7 @@ extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swar
     }
     // (as behind defrag_now; this sort is not the one whose time the policy weighs against the kernels' loss)
     defrag_schedule_restart(ctx);
-    out->sorted = 1;
+    *sorted = 1;
     if (!by_id) hipLaunchKernelGGL(k_comb_keys, dim3(gn), dim3(kBlock), 0, ctx->stream, M, S, n, nkeys, c.key);
   }
   if (by_id || !unsorted) {   // the histogram and its scan alone: the cells' starts, the ends one entry on
@@ -2309,6 +2308,44 @@ extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swar
     hipLaunchKernelGGL(k_comb_seg_add, dim3(nt), dim3(kBlock), 0, ctx->stream, (const unsigned *)c.key, n, c.C,
                        (const double *)c.tsum);
   }
+  *unsorted_out = unsorted;
+  *ends_out = ends;
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, int64_t trigger_T,
+                                         int64_t target_K, uint32_t epoch, jb_comb_plan *out) {
+  JB_RANGE("Jaybenne::CombCensus");
+  if (!ctx || !mesh || !out) return fail(JB_ERR_INVALID, "jb_comb_census_plan: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  ctx->comb.valid = ctx->weigh.valid = false;
+  jb_status st = check_swarm(swarm, "jb_comb_census_plan");
+  if (st != JB_COMPLETE) return st;
+  if (target_K < 1 || target_K > trigger_T)
+    return fail(JB_ERR_INVALID, "jb_comb_census_plan: target_K = %lld outside [1, trigger_T = %lld]", (long long)target_K,
+                (long long)trigger_T);
+  if (trigger_T >= (1ll << 32)) return fail(JB_ERR_INVALID, "jb_comb_census_plan: trigger_T beyond 2^32 - 1");
+  if (epoch >= (1u << 20)) return fail(JB_ERR_INVALID, "jb_comb_census_plan: epoch %u beyond 2^20 - 1", epoch);
+  memset(out, 0, sizeof *out);
+  const long long n = swarm->n;
+  out->n_before = out->n_after = n;
+  if (n == 0) return JB_COMPLETE;
+  const DevMesh &M = mesh->dm;
+  const CellKeys k = cell_keys(M.nblocks, M.ntot, n);
+  if ((st = check_cell_keys(k, "jb_comb_census_plan")) != JB_COMPLETE) return st;
+  const unsigned nkeys = k.nkeys;
+  const bool by_id = order_by_id(ctx);
+  const CombLayout L = comb_layout(n, k.nbins, by_id);
+  // (all of the scratch first: the sort then finds room, and a failed allocation leaves the swarm as it was)
+  st = ensure_scratch(ctx, L.words, /*slack=*/false);
+  if (st != JB_COMPLETE) return st;
+  const CombScratch c = comb_scratch(ctx, L);
+  const DevSwarm S = dev_swarm(swarm);
+  const unsigned T = (unsigned)trigger_T, K = (unsigned)target_K;
+  const int gc = comb_parts((long long)nkeys);
+  unsigned unsorted = 0u;
+  const unsigned *ends = nullptr;
+  if ((st = comb_order_and_weigh(ctx, mesh, swarm, k, L, c, &unsorted, &ends, &out->sorted)) != JB_COMPLETE) return st;
   hipLaunchKernelGGL(k_comb_decide, dim3(grid_for(ctx, n + 1)), dim3(kBlock), 0, ctx->stream, M, n, nkeys,
                      (const unsigned *)c.key, ends, (const double *)c.C, T, K, ctx->dp.key0, epoch,
                      c.kcnt, c.extra);
@@ -2339,9 +2376,180 @@ extern "C" jb_status jb_comb_census_plan(jb_context *ctx, jb_mesh *mesh, jb_swar
   ctx->comb.n_new = out->n_new_ids;
   ctx->comb.T = T;
   ctx->comb.K = K;
+  ctx->comb.global = false;
   ctx->comb.gen = ctx->scratch_gen;
   ctx->comb.ends_shift = unsorted && !by_id ? 0 : 1;
   return JB_COMPLETE;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The global comb (jb_kernel_gcomb.hpp).  Its scratch lies behind the comb's (jb_scratch_layout.hpp: gcomb_layout).
+static_assert(sizeof(jb_comb_global_plan) == 72, "nine 8-byte members");
+static_assert(kGcombStats * kGcombParts <= 2 * kCombParts, "the report's partials lie in the comb's cpart");
+static int gcomb_parts(long long ncells) {
+  const long long b = (ncells + kBlock - 1) / kBlock;
+  return (int)(b < 1 ? 1 : (b > kGcombParts ? kGcombParts : b));
+}
+
+extern "C" jb_status jb_comb_census_weigh(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, int64_t n_room,
+                                          double *e_block_host, jb_comb_global_plan *report) {
+  JB_RANGE("Jaybenne::CombCensusGlobal");
+  if (!ctx || !mesh || !e_block_host || !report) return fail(JB_ERR_INVALID, "jb_comb_census_weigh: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  ctx->comb.valid = ctx->weigh.valid = false;
+  jb_status st = check_swarm(swarm, "jb_comb_census_weigh");
+  if (st != JB_COMPLETE) return st;
+  const long long n = swarm->n;
+  if (n_room < n || n_room > swarm->capacity)
+    return fail(JB_ERR_INVALID, "jb_comb_census_weigh: n_room = %lld outside [n = %lld, capacity = %lld]", (long long)n_room,
+                n, (long long)swarm->capacity);
+  memset(report, 0, sizeof *report);
+  report->n_before = report->n_after = n;
+  const DevMesh &M = mesh->dm;
+  for (int b = 0; b < M.nblocks; ++b) e_block_host[b] = 0.0;
+  const CellKeys k = cell_keys(M.nblocks, M.ntot, n_room);
+  if ((st = check_cell_keys(k, "jb_comb_census_weigh")) != JB_COMPLETE) return st;
+  const bool by_id = order_by_id(ctx);
+  const GcombLayout G = gcomb_layout(n, n_room, k.nbins, by_id);
+  // (all of the scratch first: the sort then finds room, and a failed allocation leaves the swarm as it was)
+  if ((st = ensure_scratch(ctx, G.words, /*slack=*/false)) != JB_COMPLETE) return st;
+  if ((st = dev_grow(ctx->gcomb_eblock, sizeof(double) * (size_t)M.nblocks, "hipMalloc of the comb's block sums")) != JB_COMPLETE)
+    return st;
+  unsigned unsorted = 0u;
+  if (n > 0) {
+    const CombScratch c = comb_scratch(ctx, G.comb);
+    const unsigned *ends = nullptr;
+    if ((st = comb_order_and_weigh(ctx, mesh, swarm, k, G.comb, c, &unsorted, &ends, &report->sorted)) != JB_COMPLETE) return st;
+    ++ctx->gcomb_launches;
+    hipLaunchKernelGGL(k_gcomb_block_sums, dim3(M.nblocks), dim3(kBlock), 0, ctx->stream, M, ends, (const double *)c.C,
+                       (double *)ctx->gcomb_eblock.p);
+    JB_HIP(hipGetLastError());
+    JB_HIP(hipMemcpyAsync(e_block_host, ctx->gcomb_eblock.p, sizeof(double) * (size_t)M.nblocks, hipMemcpyDeviceToHost,
+                          ctx->stream));
+    st = comb_energy(ctx, dev_swarm(swarm), n, c.epart, &report->e_before);   // (synchronises)
+    if (st != JB_COMPLETE) return st;
+  }
+  ctx->weigh.valid = true;
+  ctx->weigh.mesh = mesh;
+  ctx->weigh.x = swarm->x;
+  ctx->weigh.n = n;
+  ctx->weigh.n_room = n_room;
+  ctx->weigh.ends_shift = unsorted && !by_id ? 0 : 1;
+  ctx->weigh.sorted = report->sorted;
+  ctx->weigh.e_before = report->e_before;
+  ctx->weigh.gen = ctx->scratch_gen;
+  return JB_COMPLETE;
+}
+
+extern "C" int64_t jb_gcomb_kernel_launches(const jb_context *ctx) { return ctx ? (int64_t)ctx->gcomb_launches : 0; }
+
+extern "C" jb_status jb_comb_census_plan_global(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, double w_total,
+                                                int64_t target_N, double band, int64_t split_max, uint32_t epoch,
+                                                jb_comb_global_plan *out) {
+  JB_RANGE("Jaybenne::CombCensusGlobal");
+  if (!ctx || !mesh || !out) return fail(JB_ERR_INVALID, "jb_comb_census_plan_global: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  ctx->comb.valid = false;
+  const bool weighed = ctx->weigh.valid;
+  ctx->weigh.valid = false;
+  jb_status st = check_swarm(swarm, "jb_comb_census_plan_global");
+  if (st != JB_COMPLETE) return st;
+  if (target_N < 1 || target_N >= (1ll << 31))
+    return fail(JB_ERR_INVALID, "jb_comb_census_plan_global: target_N = %lld outside [1, 2^31)", (long long)target_N);
+  if (!(band >= 1.0) || !(band < __builtin_huge_val()))
+    return fail(JB_ERR_INVALID, "jb_comb_census_plan_global: band = %g is not a finite number >= 1", band);
+  if (split_max < 1) return fail(JB_ERR_INVALID, "jb_comb_census_plan_global: split_max = %lld < 1", (long long)split_max);
+  if (epoch >= (1u << 20)) return fail(JB_ERR_INVALID, "jb_comb_census_plan_global: epoch %u beyond 2^20 - 1", epoch);
+  if (!weighed || ctx->weigh.mesh != mesh || ctx->weigh.x != swarm->x || ctx->weigh.n != swarm->n ||
+      ctx->weigh.gen != ctx->scratch_gen || (swarm->n > 0 && !ctx->scratch_d))
+    return fail(JB_ERR_INVALID, "jb_comb_census_plan_global: this swarm has not been weighed (jb_comb_census_weigh comes first)");
+  const long long n = swarm->n, n_room = ctx->weigh.n_room;
+  if (n + (long long)target_N >= (1ll << 32))   // (n_after <= n + target_N: the scans' totals are 32-bit words)
+    return fail(JB_ERR_INVALID, "jb_comb_census_plan_global: n + target_N beyond 2^32 - 1");
+  memset(out, 0, sizeof *out);
+  out->n_before = out->n_after = n;
+  out->sorted = ctx->weigh.sorted;
+  out->e_before = ctx->weigh.e_before;
+  if (n == 0 || !(w_total > 0.0) || !(w_total < __builtin_huge_val())) return JB_COMPLETE;   // nothing is combed
+  const DevMesh &M = mesh->dm;
+  const CellKeys k = cell_keys(M.nblocks, M.ntot, n_room);
+  const unsigned nkeys = k.nkeys;
+  const GcombLayout G = gcomb_layout(n, n_room, k.nbins, order_by_id(ctx));
+  const CombScratch c = comb_scratch(ctx, G.comb);
+  unsigned *ktgt = scratch_at<unsigned>(ctx, G.ktgt);
+  const unsigned *ends = c.hist + ctx->weigh.ends_shift;
+  const double scale = (double)target_N / w_total;
+  const int gc = gcomb_parts((long long)nkeys);
+  ctx->gcomb_launches += 2;
+  hipLaunchKernelGGL(k_gcomb_targets, dim3(gc), dim3(kBlock), 0, ctx->stream, M, nkeys, ends, (const double *)c.C, scale,
+                     band, (double)split_max, ctx->dp.key0, epoch, ktgt, c.cpart);
+  hipLaunchKernelGGL(k_gcomb_decide, dim3(grid_for(ctx, n + 1)), dim3(kBlock), 0, ctx->stream, M, n, nkeys,
+                     (const unsigned *)c.key, ends, (const double *)c.C, (const unsigned *)ktgt, ctx->dp.key0, epoch,
+                     c.kcnt, c.extra);
+  for (unsigned *data : {c.kcnt, c.extra}) scan_u32(ctx, data, n + 1, c.ssum);
+  JB_HIP(hipGetLastError());
+  unsigned totals[2] = {0u, 0u};
+  std::vector<unsigned long long> part((size_t)(kGcombStats * gc));
+  JB_HIP(hipMemcpyAsync(&totals[0], c.kcnt + n, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipMemcpyAsync(&totals[1], c.extra + n, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipMemcpyAsync(part.data(), c.cpart, sizeof(unsigned long long) * part.size(), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  out->n_after = (long long)totals[0];
+  out->n_new_ids = (long long)totals[1];
+  unsigned long long in = 0ull, outn = 0ull;
+  for (int q = 0; q < gc; ++q) {   // (the workgroups' partials in workgroup order)
+    const unsigned long long *p = &part[(size_t)(kGcombStats * q)];
+    out->cells_thinned += (int64_t)p[GS_THINNED];
+    out->cells_split += (int64_t)p[GS_SPLIT];
+    if ((int64_t)p[GS_MOST] > out->max_per_cell) out->max_per_cell = (int64_t)p[GS_MOST];
+    if ((int64_t)p[GS_TARGET] > out->max_target) out->max_target = (int64_t)p[GS_TARGET];
+    in += p[GS_IN];
+    outn += p[GS_OUT];
+  }
+  // n_after in 64 bits from the targets: the k_j of a combed cell sum to its K_k.  The scans' totals are 32-bit words
+  // and wrap where a caller's w_total is not the total (n_after <= n + target_N holds for the true one only).
+  const unsigned long long n_after64 = (unsigned long long)n - in + outn;
+  if (n_after64 > (unsigned long long)n_room) out->n_after = (int64_t)n_after64;
+  if (out->n_after > n_room)   // (no record has been written)
+    return fail(JB_ERR_CAPACITY, "jb_comb_census_plan_global: the comb needs %lld slots, n_room = %lld", (long long)out->n_after,
+                n_room);
+  ctx->comb.valid = true;
+  ctx->comb.mesh = mesh;
+  ctx->comb.x = swarm->x;
+  ctx->comb.n = n;
+  ctx->comb.n_after = out->n_after;
+  ctx->comb.n_new = out->n_new_ids;
+  ctx->comb.T = ctx->comb.K = 0u;
+  ctx->comb.global = true;
+  ctx->comb.n_room = n_room;
+  ctx->comb.gen = ctx->scratch_gen;
+  ctx->comb.ends_shift = ctx->weigh.ends_shift;
+  return JB_COMPLETE;
+}
+
+// jb_comb_census_apply for a plan of the global comb
+static jb_status gcomb_apply(jb_context *ctx, jb_swarm_view *swarm, const CellKeys &k, uint64_t id_base, jb_comb_report *out) {
+  const long long n = ctx->comb.n, n_after = ctx->comb.n_after, n_room = ctx->comb.n_room;
+  if (n_after > swarm->capacity || n_after > n_room)
+    return fail(JB_ERR_CAPACITY, "jb_comb_census_apply: %lld slots needed, %lld there", n_after, (long long)swarm->capacity);
+  const GcombLayout G = gcomb_layout(n, n_room, k.nbins, order_by_id(ctx));
+  const CombScratch c = comb_scratch(ctx, G.comb);
+  unsigned long long *rec = scratch_at<unsigned long long>(ctx, G.records());
+  const DevSwarm S = dev_swarm(swarm);
+  if (n_after > 0) {
+    ++ctx->gcomb_launches;
+    hipLaunchKernelGGL(k_gcomb_pack, dim3(grid_for(ctx, n_after)), dim3(kBlock), 0, ctx->stream, S, n, n_after, k.nkeys,
+                       (const unsigned *)c.key, (const unsigned *)c.hist + ctx->comb.ends_shift, (const double *)c.C,
+                       (const unsigned *)scratch_at<unsigned>(ctx, G.ktgt), (const unsigned *)c.kcnt,
+                       (const unsigned *)c.extra, ctx->dp.key0, (unsigned long long)id_base, rec);
+    hipLaunchKernelGGL(k_sort_unpack, dim3(grid_for(ctx, n_after)), dim3(kBlock), 0, ctx->stream, S, n_after,
+                       (const unsigned long long *)rec);
+  }
+  JB_HIP(hipGetLastError());
+  swarm->n = n_after;
+  out->n_after = n_after;
+  out->n_new_ids = ctx->comb.n_new;
+  return comb_energy(ctx, S, n_after, c.epart, &out->e_after);
 }
 
 extern "C" jb_status jb_comb_census_apply(jb_context *ctx, jb_mesh *mesh, jb_swarm_view *swarm, uint64_t id_base,
@@ -2359,6 +2567,7 @@ extern "C" jb_status jb_comb_census_apply(jb_context *ctx, jb_mesh *mesh, jb_swa
   const DevMesh &M = mesh->dm;
   const CellKeys k = cell_keys(M.nblocks, M.ntot, n);   // (within the limits: the plan was made)
   const unsigned nkeys = k.nkeys;
+  if (ctx->comb.global) return gcomb_apply(ctx, swarm, k, id_base, out);
   const CombScratch c = comb_scratch(ctx, comb_layout(n, k.nbins, order_by_id(ctx)));
   const DevSwarm S = dev_swarm(swarm);
   hipLaunchKernelGGL(k_comb_pack, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream, S, n, nkeys,
@@ -2422,7 +2631,7 @@ extern "C" jb_status jb_evaluate_radiation_moments(jb_context *ctx, jb_mesh *mes
   // (all of the scratch first: the sort then finds room, and a failed allocation leaves the swarm as it was)
   st = ensure_scratch(ctx, L.words, /*slack=*/false);
   if (st != JB_COMPLETE) return st;
-  ctx->comb.valid = false;   // (a comb plan not yet applied lived in this memory)
+  ctx->comb.valid = ctx->weigh.valid = false;   // (a comb plan not yet applied lived in this memory)
   const MomScratch m = mom_scratch(ctx, L);
   const DevSwarm S = dev_swarm(swarm);
   const int gn = grid_for(ctx, n);

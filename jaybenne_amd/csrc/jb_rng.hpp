@@ -54,6 +54,7 @@ constexpr uint32_t kRngDomainComb = 2u;      // the census comb's one offset per
 constexpr uint32_t kRngDomainBoundary = 3u;
 constexpr uint32_t kRngDomainBoundaryIx1 = 3u, kRngDomainBoundaryOx1 = 4u, kRngDomainBoundaryIx2 = 5u,
                    kRngDomainBoundaryOx2 = 6u, kRngDomainBoundaryIx3 = 7u, kRngDomainBoundaryOx3 = 8u;
+constexpr uint32_t kRngDomainCombCount = 9u;  // the global comb's count draw per cell and cycle (jb_kernel_gcomb.hpp)
 
 __device__ __forceinline__ uint64_t rng_seed_state(uint32_t seed, uint32_t domain, uint64_t id) {
   const PhiloxBlock b = philox4x32_10(0u, 0u, (uint32_t)id, (uint32_t)(id >> 32), seed, domain);

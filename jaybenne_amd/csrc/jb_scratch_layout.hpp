@@ -112,6 +112,34 @@ inline CombLayout comb_layout(long long n, long long nbins, bool by_id) {
   return c;
 }
 
+// The global comb (jb_comb_census_weigh / _plan_global / _apply), behind the comb: everything comb_layout(n) has
+// where it is -- the plan's kernels use those arrays as the comb's do, the report's kGcombStats counts per workgroup
+// (kGcombParts workgroups) lie in cpart --, then the cells' targets (n + 1 words, one at the first slot of every
+// occupied cell) and, when the move may fill more records than the swarm had slots (n_room > n), an output-record
+// span of n_room records of its own: the comb's records end where the histogram begins.  For n_room <= n the move
+// goes to the sort's records and `out` is empty.
+constexpr int kGcombStats = 6;   // per workgroup: cells thinned, cells split, largest m_k, largest K_k, and of the
+                                 // combed cells the photons they hold and the copies they come out as
+constexpr int kGcombParts = 2 * kCombParts / kGcombStats;   // workgroups whose counts fit the comb's 2 x kCombParts words
+struct GcombLayout {
+  CombLayout comb;
+  Span ktgt, out;
+  size_t words = 0;
+  const Span &records() const { return out.count ? out : comb.sort.rec; }   // where the move writes
+};
+inline GcombLayout gcomb_layout(long long n, long long n_room, long long nbins, bool by_id) {
+  GcombLayout g;
+  if (n < 0) n = 0;
+  g.comb = comb_layout(n, nbins, by_id);
+  size_t o = 8 * g.comb.words;
+  g.ktgt = {o, (size_t)n + 1, 4};
+  o += (g.ktgt.count * 4 + 7) / 8 * 8;
+  o = (o + 15) / 16 * 16;   // (records are stored 16 bytes at a time)
+  g.out = {o, n_room > n ? (size_t)n_room : 0, 8 * (size_t)kSortRecWords};
+  g.words = g.out.end() / 8;
+  return g;
+}
+
 // The moments, behind the sort: the chunks' partial sums (two places of kMomSums doubles per kMomChunk slots), the
 // counts of the report, the "out of order" flag.
 struct MomLayout {

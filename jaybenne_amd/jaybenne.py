@@ -262,6 +262,11 @@ class MeshData:
         self.comb_trigger = 0
         self.comb_history: list = []                # one dict per cycle whose comb changed the swarm
         self._comb_sorted = False                   # the last plan sorted the swarm
+        # global census comb (CombCensusGlobal; include/jaybenne_amd.h: jb_comb_census_weigh): the whole mesh is held
+        # near census_total_target photons of equal weight; 0 = off.  Not together with comb_target.
+        self.census_total_target = 0
+        self.census_total_band = 2.0
+        self.census_split_max = 64
         # radiation moments (EvaluateRadiationMoments; include/jaybenne_amd.h: jb_evaluate_radiation_moments): the
         # last call's device tensor (12, nblocks, nx3, nx2, nx1) and report; None until a host asks
         self.moments: Optional[torch.Tensor] = None
@@ -1014,6 +1019,77 @@ def CombCensus(md: MeshData) -> Optional[dict]:
     return rec
 
 
+def check_census_total(target: int, band: float, split_max: int, per_cell_max: int = 0) -> None:
+    """The ranges of the deck keys ``census_total_target``, ``census_total_band`` and ``census_split_max`` (every host
+    checks them this way), and that the global comb is not asked for together with the per-cell comb."""
+    if not 0 <= target < (1 << 31):
+        raise ValueError("census_total_target must be in [0, 2^31)")
+    if not (band >= 1.0 and np.isfinite(band)):
+        raise ValueError("census_total_band must be a finite number >= 1")
+    if split_max < 1:
+        raise ValueError("census_split_max must be >= 1")
+    if target > 0 and per_cell_max > 0:
+        raise ValueError("census_total_target and census_per_cell_max: one comb at a time -- the global comb deals the "
+                         "cells their shares itself")
+
+
+def CombCensusGlobal(md: MeshData) -> Optional[dict]:
+    """Census population control for the whole mesh at the end of a cycle (the reference has none): the swarm is held
+    near ``md.census_total_target = N`` photons of equal weight.  N is dealt to the cells in proportion to the census
+    energy they hold; a cell whose count is off its share by more than the factor ``md.census_total_band`` is combed to
+    its share -- thinned or split, at most to ``md.census_split_max`` times its count -- and keeps its energy
+    (include/jaybenne_amd.h: ``jb_comb_census_weigh`` / ``_plan_global`` / ``_apply``).  The block sums of the census
+    energy are gathered by global block id and added by ``jb_source_energy_total``, so every rank divides by the same
+    total; ids are dealt as ``CombCensus`` deals them.  Returns the cycle's record (also appended to
+    ``md.comb_history``, ``mode="global"``) when the comb changed a swarm anywhere, else None."""
+    N = int(md.census_total_target)
+    if N <= 0:
+        return None
+    if md.replicated:
+        raise ValueError("the census comb needs the photons of a cell on one rank: not with a replicated mesh")
+    band, S = float(md.census_total_band), int(md.census_split_max)
+    check_census_total(N, band, S, int(md.comb_target))
+    md._sync_stream()
+    n = int(md.sv.n)
+    n_room = min(n + N, S * n)          # (n_after <= n + N: every combed cell had a photon)
+    md.reserve(n_room)
+    plan = _lib.CombGlobalPlan()
+    e_local = np.zeros(md.nblocks, dtype=np.float64)
+    _lib.check(md.lib.jb_comb_census_weigh(md.pkg.ctx, md.handle, C.byref(md.sv), n_room, e_local.ctypes.data,
+                                           C.byref(plan)))
+    e_gid = np.ascontiguousarray(gather_block_energies(md, e_local), dtype=np.float64)
+    w_total = float(md.lib.jb_source_energy_total(e_gid.ctypes.data, int(md.mesh.nblocks)))
+    if w_total > 0.0 and np.isfinite(w_total):
+        _lib.check(md.lib.jb_comb_census_plan_global(md.pkg.ctx, md.handle, C.byref(md.sv), w_total, N, band, S,
+                                                     int(md.cycle), C.byref(plan)))
+    md._comb_sorted = bool(plan.sorted)
+    changed_here = int(plan.cells_thinned) + int(plan.cells_split)
+    new_ids = np.zeros(md.nranks, dtype=np.int64)
+    new_ids[md.rank] = int(plan.n_new_ids)
+    changed = np.zeros(md.nranks, dtype=np.int64)
+    changed[md.rank] = changed_here
+    if md.comm is not None and md.nranks > 1:
+        both = md.comm.allreduce_sum_int64(np.concatenate([new_ids, changed]))
+        new_ids, changed = both[:md.nranks], both[md.nranks:]
+    rec = None
+    id_base = md.next_id + int(new_ids[:md.rank].sum())
+    if changed_here > 0:
+        rep = _lib.CombReport()
+        _lib.check(md.lib.jb_comb_census_apply(md.pkg.ctx, md.handle, C.byref(md.sv), id_base, C.byref(rep)))
+        rec = dict(n_after=int(rep.n_after), n_new_ids=int(rep.n_new_ids), e_after=float(rep.e_after))
+    elif int(changed.sum()) > 0:   # (another rank's swarm changed: the cycle is on record here too)
+        rec = dict(n_after=int(plan.n_after), n_new_ids=0, e_after=float(plan.e_before))
+    md.next_id += int(new_ids.sum())
+    if rec is not None:
+        # (n_eff = (sum w)^2 / sum w^2 is left out: the plan forms no sum of squared weights)
+        rec.update(mode="global", cycle=md.cycle, n_before=int(plan.n_before), id_base=id_base,
+                   cells_combed=changed_here, cells_thinned=int(plan.cells_thinned), cells_split=int(plan.cells_split),
+                   max_per_cell=int(plan.max_per_cell), max_target=int(plan.max_target),
+                   e_before=float(plan.e_before), w_total=w_total, scale=float(N) / w_total)
+        md.comb_history.append(rec)
+    return rec
+
+
 def EstimateTimestepMesh(md: MeshData) -> float:
     """reference jaybenne.cpp:271-275"""
     return float(md.lib.jb_estimate_timestep(md.pkg.ctx))
@@ -1292,10 +1368,13 @@ def _radiation_step(md: MeshData, t_start: float, dt: float) -> TaskStatus:
 def _comb_and_defrag_after_step(md: MeshData, events: int) -> None:
     """The end of a cycle: the census comb where it is on, then DefragParticles' schedule.  With the comb off this
     is ``_defrag_after_step`` and nothing else."""
-    if md.comb_target <= 0:
+    if md.comb_target <= 0 and md.census_total_target <= 0:
         _defrag_after_step(md, events)
         return
-    CombCensus(md)
+    if md.census_total_target > 0:
+        CombCensusGlobal(md)
+    else:
+        CombCensus(md)
     _defrag_after_step(md, events, sorted_by_comb=md._comb_sorted)
 
 

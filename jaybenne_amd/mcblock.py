@@ -369,6 +369,19 @@ class McblockDriver:
                              "a replicated mesh spreads them over the ranks")
         self.md.comb_target = target
         self.md.comb_trigger = jb.comb_trigger_of(target, trigger)
+        # (nor these: the global census comb -- the whole mesh is held near census_total_target photons of equal
+        # weight; a cell is combed when its count is off its share by more than the factor census_total_band, and
+        # grows to at most census_split_max times its count; 0 = off)
+        total = pin.GetOrAddInteger("jaybenne_amd", "census_total_target", 0)
+        band = pin.GetOrAddReal("jaybenne_amd", "census_total_band", 2.0)
+        split_max = pin.GetOrAddInteger("jaybenne_amd", "census_split_max", 64)
+        jb.check_census_total(total, band, split_max, target)
+        if total > 0 and replicated:
+            raise ValueError("census_total_target: the census comb needs the photons of a cell on one rank; "
+                             "a replicated mesh spreads them over the ranks")
+        self.md.census_total_target = total
+        self.md.census_total_band = band
+        self.md.census_split_max = split_max
         # (nor this one: the order of the photons within a cell behind a sort -- any, or id: the canonical order)
         order = deck_cell_order(pin)
         if order != self.md.cell_order:
