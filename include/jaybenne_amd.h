@@ -371,9 +371,14 @@ int jb_get_arithmetic(const jb_context *ctx);
  * jb_last_transport_grid: the largest number of workgroups any persistent tracking launch of the
  * last transport call on this mesh used (a call makes up to three launches), 0 before the first.
  * JB_TRANSPORT_MAX_BLOCKS=k in the environment at jb_initialize caps it at k (a test aid: the
- * results do not depend on the grid; unset or <= 0: no cap). */
+ * results do not depend on the grid; unset or <= 0: no cap).
+ * jb_last_transport_unit_cell: what the variant string does not say of a "k_imc_cell<..., lean>"
+ * launch -- 0: position and direction in real units; 1: in units of the half cell width (every
+ * resident block has the same power-of-two cell widths: the same results bit for bit); 2: the
+ * same with all active widths equal.  0 for every other kernel and before the first launch. */
 const char *jb_last_transport_variant(const jb_mesh *mesh);
 int jb_last_transport_grid(const jb_mesh *mesh);
+int jb_last_transport_unit_cell(const jb_mesh *mesh);
 int jb_mesh_exact_geometry(const jb_mesh *mesh);
 /* All-DDMC meshes: the number of DISTINCT step records UpdateDerivedTransportFields found among the
  * resident cells this cycle, as the last jb_transport_photons_ddmc call read it back (0 before the

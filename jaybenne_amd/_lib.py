@@ -276,6 +276,7 @@ PROTOTYPES = {
                                          _int]),
     "jb_last_transport_variant": (C.c_char_p, [_vp]),
     "jb_last_transport_grid": (_int, [_vp]),
+    "jb_last_transport_unit_cell": (_int, [_vp]),
     "jb_mesh_exact_geometry": (_int, [_vp]),
     "jb_mesh_ddmc_classes": (_int, [_vp]),
     "jb_get_transport_stats": (_int, [_vp, C.POINTER(TransportStats), _int]),

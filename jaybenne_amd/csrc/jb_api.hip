@@ -219,6 +219,8 @@ struct jb_mesh {
   const DevMesh *dm_dev = nullptr;  // copy of dm in device memory (k_hybrid reads the view through it)
   const int *nbr_dq = nullptr;      // k_imc_cell: change of the cell's byte offset per (block, face) crossing
   bool uniform_geom = false;        // every resident block has the cell widths of block 0 (k_imc_cell<.., UNIFORM>)
+  bool equal_h = false;             // the active cell widths of block 0 are equal (k_imc_cell<.., UNITCELL, EQUALH>)
+  int last_unit_cell = 0;           // the last transport call's plan: 0 no unit-cell form, 1 UNITCELL, 2 with EQUALH
   // "some cell takes IMC steps" (DevMesh::not_all_ddmc) as the host last read it: -1 = not since
   // UpdateDerivedTransportFields rewrote it (the first DDMC transport call of a cycle reads it back,
   // one synchronisation; the further transport iterations of a multi-rank cycle reuse the answer)
@@ -765,6 +767,8 @@ extern "C" jb_status jb_mesh_create(jb_context *ctx, const jb_mesh_view *v, jb_m
     m->uniform_geom = true;
     for (int b = 1; b < v->nblocks; ++b)
       for (int d = 0; d < 3; ++d) m->uniform_geom = m->uniform_geom && v->blk_dx[3 * b + d] == v->blk_dx[d];
+    m->equal_h = v->nblocks > 0;
+    for (int d = 1; d < v->ndim; ++d) m->equal_h = m->equal_h && v->blk_dx[d] == v->blk_dx[0];
   }
   int maxrank = 0;
   for (int g = 0; g < v->nblocks_total; ++g) maxrank = v->owner[g] > maxrank ? v->owner[g] : maxrank;
@@ -1608,17 +1612,26 @@ static void launch_k_transport(jb_context *ctx, const jb_mesh *mesh, const Trans
   });
 }
 
-// k_imc_cell<NDIM, TALLY, NOABS, UNIFORM>
+// k_imc_cell<NDIM, TALLY, NOABS, UNIFORM>, or k_imc_cell_unit<NDIM, TALLY, NOABS, EQUALH> where the plan says unit_cell
+// (in 1-D there is one active width: always EQUALH)
 template <int NDIM>
 static void launch_k_imc_cell(jb_context *ctx, const jb_mesh *mesh, const TransportPlan &p, const DevSwarm &S,
                               double t_start, double dt, long long first, long long last) {
   with_bool(p.tally, [&](auto tc) {
     with_bool(p.noabs, [&](auto nc) {
-      with_bool(p.uniform, [&](auto uc) {
-        launch_persistent<k_imc_cell<NDIM, decltype(tc)::value, decltype(nc)::value, decltype(uc)::value>>(
-            ctx, last - first, 0, Occupancy::cached, track_dm_dev(mesh), ctx->dp, S, t_start, dt, first, last,
-            ctx->counters_d, mesh->nbr_dq);
-      });
+      constexpr bool T = decltype(tc)::value, NA = decltype(nc)::value;
+      const auto go = [&](auto kc) {
+        launch_persistent<decltype(kc)::value>(ctx, last - first, 0, Occupancy::cached, track_dm_dev(mesh), ctx->dp, S,
+                                               t_start, dt, first, last, ctx->counters_d, mesh->nbr_dq);
+      };
+      if (!p.uniform) return go(kernel_c<k_imc_cell<NDIM, T, NA, false>>{});
+      if constexpr (kUnitCellForm) {
+        if (p.unit_cell && (p.equal_h || NDIM == 1)) return go(kernel_c<k_imc_cell_unit<NDIM, T, NA, true>>{});
+        if constexpr (NDIM > 1) {
+          if (p.unit_cell) return go(kernel_c<k_imc_cell_unit<NDIM, T, NA, false>>{});
+        }
+      }
+      go(kernel_c<k_imc_cell<NDIM, T, NA, true>>{});
     });
   });
 }
@@ -1750,6 +1763,8 @@ static jb_status launch_transport(jb_context *ctx, jb_mesh *mesh, const DevSwarm
   in.exact_geom = mesh->exact_geom;
   in.cell_ok = mesh->cell_ok;
   in.uniform_geom = mesh->uniform_geom;
+  in.equal_h = mesh->equal_h;
+  in.unit_cell_form = kUnitCellForm;
   in.lean_arith = ctx->lean_arith;
   in.no_imc_cell = ctx->no_imc_cell;
   in.coop_gather = ctx->coop_gather;
@@ -1758,6 +1773,7 @@ static jb_status launch_transport(jb_context *ctx, jb_mesh *mesh, const DevSwarm
   in.max_classes = ctx->max_classes;
   const TransportPlan plan = select_transport(in);
   variant_name(plan, mesh->last_variant, sizeof mesh->last_variant);
+  mesh->last_unit_cell = plan.unit_cell ? (plan.equal_h ? 2 : 1) : 0;
   switch (plan.family) {
   case Family::k_transport: launch_k_transport<NDIM>(ctx, mesh, plan, S, t_start, dt, first, last); break;
   case Family::k_imc_cell: launch_k_imc_cell<NDIM>(ctx, mesh, plan, S, t_start, dt, first, last); break;
@@ -1865,6 +1881,7 @@ extern "C" const char *jb_last_transport_variant(const jb_mesh *mesh) {
   return mesh ? mesh->last_variant : "";
 }
 extern "C" int jb_last_transport_grid(const jb_mesh *mesh) { return mesh ? mesh->last_grid : 0; }
+extern "C" int jb_last_transport_unit_cell(const jb_mesh *mesh) { return mesh ? mesh->last_unit_cell : 0; }
 extern "C" int jb_mesh_exact_geometry(const jb_mesh *mesh) { return mesh && mesh->exact_geom; }
 extern "C" int jb_mesh_ddmc_classes(const jb_mesh *mesh) { return mesh ? mesh->nclass_host : 0; }
 extern "C" jb_status jb_set_arithmetic(jb_context *ctx, int mode) {
@@ -3930,6 +3947,10 @@ __global__ void k_dbg_stream_start(uint32_t seed, unsigned long long id, unsigne
 }
 __global__ void k_dbg_math(int which, const double *x, int n, double *out) {
   load_math_tables<true, true, true, true, true>();
+  // (cases 18 / 19 carry a shift k in the bits above the low eight: 18 | k << 8)
+  const int shift = which >> 8;
+  which &= 0xff;
+  const double p2 = __longlong_as_double((long long)(1023 + shift) << 52);  // 2^k
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     double s, c;
     switch (which) {
@@ -3950,6 +3971,10 @@ __global__ void k_dbg_math(int which, const double *x, int n, double *out) {
     case 15: out[i] = m_log_lean<false, true>(x[i]); break;
     case 16: m_sincos2pi<false, true>(x[i], s, c); out[i] = s; break;   // grid point by the magic constant
     case 17: m_sincos2pi<false, true>(x[i], s, c); out[i] = c; break;
+    // what k_imc_cell<.., UNITCELL> asks of the hardware's seeds: the lean reciprocal of x 2^k times 2^k and the
+    // lean square root of x 4^k over 2^k are those of x (k = 0), bit for bit
+    case 18: out[i] = m_rcp_once(x[i] * p2) * p2; break;
+    case 19: out[i] = m_sqrt_lean((x[i] * p2) * p2) / p2; break;
     default: out[i] = m_sqrt_lean(x[i]); break;
     }
   }

@@ -302,6 +302,14 @@ __device__ __forceinline__ double uniform_f64(double v) {
   const unsigned hi = sgpr_copy((unsigned)(q >> 32));
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
+// ... and the other way: a wave-uniform double parked in a VECTOR register pair for good (an operand that inline
+// asm reads word by word from vector registers: left scalar, the compiler copies it over again on every use)
+__device__ __forceinline__ double vgpr_f64(double v_uniform) {
+  int lo, hi;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(lo) : "s"(__double2loint(v_uniform)));
+  asm volatile("v_mov_b32 %0, %1" : "=v"(hi) : "s"(__double2hiint(v_uniform)));
+  return __hiloint2double(hi, lo);
+}
 __device__ __forceinline__ const double *sgpr_copy_ptr(const double *p) {
   const unsigned long long q = (unsigned long long)p;
   const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)q);

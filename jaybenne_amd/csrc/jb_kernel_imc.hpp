@@ -38,6 +38,26 @@
 // reference's.  The stated tolerance of the lean variant (include/jaybenne_amd.h) is unchanged and
 // is what tests/test_gpu_lean.py / test_gpu_accuracy.py hold this kernel to; bit-for-bit parity with
 // the oracle is the exact variant's (k_transport<.., EXACT, !LEAN>).
+//
+// UNITCELL (k_imc_cell_unit): where every resident block has ONE cell size and the widths are powers of two (every
+// stepdiff deck; select_transport: uniform_geom && exact_geom) the lane carries p' = p / h and omega' = omega / h per
+// active axis instead of p and omega -- h is then a wave-uniform power of two and h |1/omega| an exponent shift spent
+// three times per pass on a constant.  1 / omega' = h / omega, so the distance to the face ahead is
+// fma(-p', 1/omega', |1/omega'|), one instruction with the magnitude as a source modifier; the face test is
+// |p'| > (h - eps_imc dx) / h, the same double on every axis (one register pair for three).  Distances keep their
+// units: d_rem, the mean free paths, dx_push and the move p' = fma(omega', d, p') are as above.  The scatter forms
+// the new direction on the scale of its polar axis (scatter_dir<.., UNITCELL>: the stream's mantissa under the
+// exponent of 2 / h_z, 1 / h_z^2 - mu'^2, the lean square root of it), with two more multiplications by powers of two
+// where the widths differ between axes (EQUALH = false).  The service phase scales on load (omega' = (v rc) (1/h),
+// p' = p (1/h) behind `localise`) and unscales in front of every consumer of real coordinates (`materialise` in
+// `relocate` and in the write-back, the velocity as (omega' h) c); the wall's sign flips act on the scaled values; an
+// IS_DONE_RAW lane never leaves real units; an inactive axis keeps its coordinate and carries its direction component
+// on the x scale.  Every operand is the unscaled form's times a power of two, so every rounded result is (given that
+// v_rcp_f64 and v_rsq_f64 commute with powers of two and four: jb_debug_math 18 / 19,
+// tests/test_gpu_imc_unit_cell.py): the stored attributes are the unscaled form's bit for bit.  By static count
+// 3 vector instructions fewer per stepping pass and 121 registers for 128; measured on C2 49.25 -> 48.39 ms per step
+// (DESIGN 4.1).  A checked-build report still names p in real units.  Uniform meshes with other widths (1/24), blocks of
+// several sizes and k_hybrid keep the form above; -DJB_IMC_PARENT_COORDS builds the library without this one.
 #pragma once
 
 #include "jb_kernels.hpp"
@@ -102,11 +122,10 @@ enum { IS_IDLE = 0, IS_RUN = 1, IS_DONE = 2, IS_DONE_RAW = 3 };
 constexpr bool kWideLog = JB_IMC_WIDE_LOG != 0;
 
 
-template <int NDIM, bool TALLY, bool NOABS, bool UNIFORM>
-__global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
-                                          : UNIFORM ? JB_IMC_WAVES_PER_SIMD_UNIFORM : JB_IMC_WAVES_PER_SIMD)
-    k_imc_cell(const DevMesh *__restrict__, DevParams, DevSwarm, double, double, long long, long long,
-               unsigned long long *, const int *) {
+// The kernel's body: k_imc_cell<.., UNIFORM> and k_imc_cell_unit<.., EQUALH> (= UNIFORM, UNITCELL) below are its two
+// entry points, with one argument list.
+template <int NDIM, bool TALLY, bool NOABS, bool UNIFORM, bool UNITCELL, bool EQUALH>
+__device__ __forceinline__ void imc_cell_body() {
   // The arguments are read where they are used, from the kernel-argument segment (scalar loads), and
   // the mesh view through a pointer to its copy in device memory: the event loop needs four scalars
   // of it (base of the scattering mean free paths, two strides), everything else is service-phase
@@ -167,7 +186,55 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
     cg.mx = cg.hx - kEpsImc * d0; cg.my = cg.hy - kEpsImc * d1; cg.mz = cg.hz - kEpsImc * d2;
     cg.dxp = dmin(d0, dmin(d1, d2));
   }
+  // UNITCELL: the scales.  1 / h per axis for position and direction; an inactive axis, whose position is the
+  // coordinate itself and never moves, keeps its position and carries its direction component on the x scale (the
+  // scatter forms all three components on the scale of its polar axis, z: no multiply to come back in 1-D, none in
+  // 2-D where hx = hy).  All of it wave-uniform integer arithmetic on exponents, once per wave.
+  static_assert(!UNITCELL || UNIFORM, "UNITCELL needs wave-uniform cell widths");
+  static_assert(!EQUALH || UNITCELL, "EQUALH is a form of UNITCELL");
+  double ihx = 1.0, ihy = 1.0, ihz = 1.0;   // 1 / h of the axis' scale
+  double shy = 1.0, shz = 1.0;              // h of the y and z scales (cg.hy, cg.hz where the axis is active)
+  UnitScale us{0, 0.0, 0.0, 0.0, 1.0, 1.0};
+  if constexpr (UNITCELL) {
+    // (EQUALH: one half width, said once, so that one register pair holds it and one its reciprocal)
+    if constexpr (EQUALH) { cg.hy = multi_d ? cg.hx : cg.hy; cg.hz = three_d ? cg.hx : cg.hz; }
+    shy = multi_d ? cg.hy : cg.hx;
+    shz = three_d ? cg.hz : cg.hx;
+    ihx = uniform_f64(m_inv_pow2(cg.hx));
+    ihy = EQUALH ? ihx : uniform_f64(m_inv_pow2(shy));
+    ihz = EQUALH ? ihx : uniform_f64(m_inv_pow2(shz));
+    // (h - eps_imc dx) / h: the same double on every axis (in vector registers: the nudge reads it word by word)
+    cg.mx = vgpr_f64(m_mul_pow2(uniform_f64(cg.mx), ihx));
+    cg.my = cg.mx; cg.mz = cg.mx;
+    // (each pinned to a scalar register pair: every instruction of the loop that reads one reads only that one)
+    cg.qmin = uniform_f64(m_mul_pow2(m_mul_pow2(m_mul_pow2(1.0e-250, ihx), multi_d ? ihy : 1.0), three_d ? ihz : 1.0));
+    const double two_ihz = m_mul_pow2(2.0, ihz);
+    us.xi_exp = (int)sgpr_copy((unsigned)__double2hiint(two_ihz));
+    us.xi_off = uniform_f64(m_mul_pow2(0.99999999999999988897769753748434595763683319091796875, two_ihz));  // (1 - 2^-53) 2 / h_z
+    us.one = uniform_f64(ihz);
+    us.s0 = uniform_f64(m_mul_pow2(ihz, ihz));
+    if constexpr (!EQUALH) { us.kx = uniform_f64(m_mul_pow2(shz, ihx)); us.ky = uniform_f64(m_mul_pow2(shz, ihy)); }
+  }
+  // to and from the units of the half cell width (exact: powers of two); no-ops in the other forms
+  auto scale_p = [&]() {
+    if constexpr (UNITCELL) {
+      px *= ihx;
+      if (multi_d) py *= ihy;
+      if (three_d) pz *= ihz;
+    }
+  };
+  auto unscale_p = [&]() {
+    if constexpr (UNITCELL) {
+      px *= cg.hx;
+      if (multi_d) py *= cg.hy;
+      if (three_d) pz *= cg.hz;
+    }
+  };
   double lam_a = 0.0, lam_s = 0.0;          // mean free paths of the photon's cell, or the ghost code
+  // (checked build) a report names the position relative to the cell centre in real units in either form
+  JB_INV_STMT(auto inv_rx = [&]() { return UNITCELL ? px * cg.hx : px; };)
+  JB_INV_STMT(auto inv_ry = [&]() { return UNITCELL && multi_d ? py * cg.hy : py; };)
+  JB_INV_STMT(auto inv_rz = [&]() { return UNITCELL && three_d ? pz * cg.hz : pz; };)
   JB_INV_STMT(bool inv_collided = false;)   // (checked build) the lane's last step ended in a collision
 
   auto fetch_lam = [&]() {
@@ -223,6 +290,7 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
   auto relocate = [&]() {
     double x, y, z;
     int i, j, k;
+    unscale_p();  // (UNITCELL: real coordinates from here; the direction only changes sign below, on any scale)
     materialise(x, y, z, i, j, k);
     // (inactive axes: p holds the coordinate itself)
     if (!apply_swarm_bcs<NDIM>(M, x, y, z, ox, oy, oz)) {
@@ -248,6 +316,7 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
     load_block(M, b, B);
     xtoijk<NDIM>(M, B, x, y, z, i, j, k);
     localise(x, y, z, i, j, k);
+    scale_p();
     ls = (drem > 0.0) ? IS_RUN : IS_DONE;
     fetch_lam();
   };
@@ -256,6 +325,13 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
     // ================================ SERVICE ================================
     ++c_service;
     if (ls == IS_DONE || ls == IS_DONE_RAW) {
+      if constexpr (UNITCELL) {
+        // a tracked lane back to real units (IS_DONE_RAW never left them; an absolute position is one already)
+        if (ls == IS_DONE) {
+          if (!abs_pos) unscale_p();
+          ox *= cg.hx; oy *= shy; oz *= shz;
+        }
+      }
       double x = px, y = py, z = pz;
       int ip = 0, jp = 0, kp = 0;
       if (!abs_pos) {
@@ -328,6 +404,10 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
           if (t < t_end) {
             drem = vv * (t_end - t);
             ox *= P.rc; oy *= P.rc; oz *= P.rc;
+            if constexpr (UNITCELL) {  // (v rc rounded as ever, then the exact scaling)
+              ox *= ihx; oy *= ihy; oz *= ihz;
+              scale_p();
+            }
             ls = IS_RUN;
           } else {  // already at census: nothing to track, nothing to convert
             drem = t;
@@ -372,7 +452,7 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
       if (cross_m != 0ull) {
         if (cross) {
           // (checked build) EVENT_OFF_BLOCK: the step that took the photon into this ghost cell had no collision
-          JB_INV_OFF_BLOCK(JB_INV_FAM_IMC_CELL, inv_collided, false, block_of(), 0, 0, 0, px, py, pz, n, S.id, (void)0);
+          JB_INV_OFF_BLOCK(JB_INV_FAM_IMC_CELL, inv_collided, false, block_of(), 0, 0, 0, inv_rx(), inv_ry(), inv_rz(), n, S.id, (void)0);
           const int code = __double2hiint(lam_s);
           if ((code & kGhostTable) == 0) {
             b = block_of();
@@ -408,19 +488,21 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
       JB_INV_STMT(bool inv_bad = false;)
       JB_INV_STMT({
         int ib = -1, ii = 0, ij = 0, ik = 0, ax = 0;
-        const double pp[3] = {px, py, pz}, hh[3] = {cg.hx, cg.hy, cg.hz};
+        // (UNITCELL: |p'| <= 1 on the active axes)
+        const double pp[3] = {px, py, pz};
+        const double hh[3] = {UNITCELL ? 1.0 : cg.hx, UNITCELL ? 1.0 : cg.hy, UNITCELL ? 1.0 : cg.hz};
         const bool pos = inv::local_position_ok(NDIM, pp, hh, ax);
         const unsigned cell = (qoff % blk_bytes) >> 3;
         const bool idx = cell < (unsigned)M.ntot &&
                          inv::cell_interior(M, (unsigned long long)(qoff / blk_bytes) * (unsigned long long)M.ntot + cell,
                                             ib, ii, ij, ik);
-        JB_INV_PASS_PRED(JB_INV_FAM_IMC_CELL, stepping, pos, idx, ax, ib, ii, ij, ik, px, py, pz, n, S.id,
+        JB_INV_PASS_PRED(JB_INV_FAM_IMC_CELL, stepping, pos, idx, ax, ib, ii, ij, ik, inv_rx(), inv_ry(), inv_rz(), n, S.id,
                          { inv_bad = true; ls = IS_IDLE; });
       })
       if (stepping JB_INV_STMT(&& !inv_bad)) {
         bool is_absorbed, is_scattered, hit_any;
         unsigned long long hit_m;
-        imc_step_cell<NDIM, NOABS, UNIFORM, kWide, kMasked>(cg, sy, sz, lam_a, lam_s, rng, drem, px, py, pz, ox, oy, oz,
+        imc_step_cell<NDIM, NOABS, UNIFORM, kWide, kMasked, UNITCELL>(cg, sy, sz, lam_a, lam_s, rng, drem, px, py, pz, ox, oy, oz,
                                                      qoff, is_absorbed, is_scattered, hit_any, &hit_m, fetch_lam);
         // (for the next pass, ahead of the scatter -- and only where the step changed the cell: a lane that
         // scattered, was absorbed or reached census inside its cell holds that cell's values already; on
@@ -456,7 +538,7 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
           }
           ls = IS_DONE;
         } else {
-          if (is_scattered && collide) scatter_dir<true>(rng, ox, oy, oz);  // transport.cpp:165-170
+          if (is_scattered && collide) scatter_dir<true, UNITCELL, EQUALH>(rng, ox, oy, oz, us);  // transport.cpp:165-170
           if (census && !off) ls = IS_DONE;
         }
       }
@@ -474,6 +556,24 @@ __global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
     atomicAdd(&counters[CNT_PASSES], c_evp >> 40);
     atomicAdd(&counters[CNT_SERVICE], (unsigned long long)c_service);
   }
+}
+
+// position and direction in real units: any cell widths
+template <int NDIM, bool TALLY, bool NOABS, bool UNIFORM>
+__global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD
+                                          : UNIFORM ? JB_IMC_WAVES_PER_SIMD_UNIFORM : JB_IMC_WAVES_PER_SIMD)
+    k_imc_cell(const DevMesh *__restrict__, DevParams, DevSwarm, double, double, long long, long long,
+               unsigned long long *, const int *) {
+  imc_cell_body<NDIM, TALLY, NOABS, UNIFORM, false, false>();
+}
+
+// ... in units of the half cell width: one cell size on every resident block, power-of-two widths (a kernel name of
+// its own: tools and tests find k_imc_cell's instantiations by the four arguments above)
+template <int NDIM, bool TALLY, bool NOABS, bool EQUALH>
+__global__ void __launch_bounds__(kBlock, NDIM < 3 ? JB_IMC_WAVES_PER_SIMD_LOWD : JB_IMC_WAVES_PER_SIMD_UNIFORM)
+    k_imc_cell_unit(const DevMesh *__restrict__, DevParams, DevSwarm, double, double, long long, long long,
+               unsigned long long *, const int *) {
+  imc_cell_body<NDIM, TALLY, NOABS, true, true, EQUALH>();
 }
 
 }  // namespace jb

@@ -51,6 +51,14 @@ namespace jb {
 #ifndef JB_IMC_PARENT_AZIMUTH
 #define JB_IMC_PARENT_AZIMUTH 0
 #endif
+// -DJB_IMC_PARENT_COORDS (`make parent_coords`): no launch takes k_imc_cell's UNITCELL form (position and direction
+// in units of the half cell width, jb_kernel_imc.hpp) -- the library tests/test_gpu_imc_unit_cell.py compares the
+// release with, bit for bit, and its partner in an A/B.  Independent of the three above.
+#ifdef JB_IMC_PARENT_COORDS
+constexpr bool kUnitCellForm = false;
+#else
+constexpr bool kUnitCellForm = true;
+#endif
 
 // fma through the 3-address VOP3 form.  Left to itself the compiler turns a Horner step
 // p = fma(r, p, C) with a loop-invariant constant C into "v_mov_b64 acc, C; v_fmac_f64 acc, r, p"
@@ -89,6 +97,29 @@ __device__ __forceinline__ double m_fnma(double a, double b, double c) {
   asm("v_fma_f64 %0, -%1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
   return d;
 #endif
+}
+
+// fma(-a, b, |b|): the negation and the magnitude of the addend as source modifiers of the one instruction
+// (imc_step_cell<.., UNITCELL>: the distance to the face ahead in units of the half cell width)
+__device__ __forceinline__ double m_fnma_abs(double a, double b) {
+#ifdef JB_NO_ASM_FMA
+  return fma(-a, b, fabs(b));
+#else
+  double d;
+  asm("v_fma_f64 %0, -%1, %2, |%2|" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+#endif
+}
+
+// 1 / h for h a normal power of two, exactly: the exponent field mirrored about the bias (integer arithmetic on a
+// wave-uniform value: scalar instructions, no division)
+__device__ __forceinline__ double m_inv_pow2(double h) {
+  return __longlong_as_double(0x7fe0000000000000ll - __double_as_longlong(h));
+}
+// x p for p a positive normal power of two and a normal product, exactly: p's exponent added to x's (scalar integer
+// arithmetic where both are wave-uniform; the product of two doubles would be formed by the vector unit, per lane)
+__device__ __forceinline__ double m_mul_pow2(double x, double p) {
+  return __longlong_as_double(__double_as_longlong(x) + (__double_as_longlong(p) - 0x3ff0000000000000ll));
 }
 
 // min of two non-NaN numbers / minNum when one is NaN: one v_min_f64 (std::min written as

@@ -511,11 +511,17 @@ struct NoGather {
 // hit_mask, where asked for: hit_any of the wave's lanes.
 struct CellGeom {
   double hx, hy, hz, mx, my, mz, dxp;
+  double qmin;  // UNITCELL: 1e-250 / (hx hy hz), the small-product threshold of the reciprocals on the scaled direction
 };
 // MASKED: the nudge and the re-indexing under exec masks (nudge_reindex_masked above) instead of selects;
 // `gather`, where given, is called on the lanes of hit_any once the offset names the new cell.
-template <int NDIM, bool NOABS, bool UNIFORM = false, bool WIDELOG = false, bool MASKED = false, class Rng,
-          class Gather = NoGather>
+// UNITCELL (with UNIFORM, power-of-two cell widths: jb_kernel_imc.hpp): p and omega arrive divided by the half cell
+// width of their axis; the distances -- dx_push, dx_sc, dx_abs, d_rem -- keep their units.  The reciprocal of
+// omega / h is h / omega, so the distance to the face ahead is fma(-p', r', |r'|), one instruction; the face test
+// is |p'| > g.mx on every axis, g.mx = g.my = g.mz = (h - eps_imc dx) / h.  Every operand is the unscaled form's
+// times a power of two, so every rounded result is: the same bits once scaled back.
+template <int NDIM, bool NOABS, bool UNIFORM = false, bool WIDELOG = false, bool MASKED = false, bool UNITCELL = false,
+          class Rng, class Gather = NoGather>
 __device__ __forceinline__ void imc_step_cell(const CellGeom &g, int sy, int sz, double lam_a, double lam_s,
                                               Rng &rng, double &drem, double &px, double &py, double &pz,
                                               double ox, double oy, double oz, unsigned &qoff,
@@ -523,6 +529,7 @@ __device__ __forceinline__ void imc_step_cell(const CellGeom &g, int sy, int sz,
                                               unsigned long long *hit_mask = nullptr, Gather gather = Gather()) {
   constexpr bool multi_d = NDIM >= 2, three_d = NDIM == 3;
   constexpr int sx = 8;
+  static_assert(!UNITCELL || UNIFORM, "the half cell width is a unit only where it is wave-uniform");
   // ---- transport_utils.hpp:118-134: distances to collision, census, cell faces
   double dx_abs = 0.0;
   if constexpr (NOABS) rng.skip();
@@ -538,7 +545,8 @@ __device__ __forceinline__ void imc_step_cell(const CellGeom &g, int sy, int sz,
   if constexpr (three_d) {
     // the three reciprocals from ONE hardware reciprocal, of the product (imc_step_dir)
     const double pxy = ox * oy, q = pxy * oz;
-    if (fabs(q) > 1.0e-250) {
+    // (UNITCELL: the product is the unscaled one over hx hy hz, and so is the threshold: the same lanes)
+    if (fabs(q) > (UNITCELL ? g.qmin : 1.0e-250)) {
       const double r = m_rcp_once(q);
       const double roz = r * oz;
       rz = r * pxy; rx = roz * oy; ry = roz * ox;
@@ -551,9 +559,15 @@ __device__ __forceinline__ void imc_step_cell(const CellGeom &g, int sy, int sz,
   }
   // (a direction component that is exactly zero: NaN, which minNum ignores -- the reference's
   // third branch)
-  dx_push = m_min(dx_push, m_fnma(px, rx, g.hx * fabs(rx)));
-  if (multi_d) dx_push = m_min(dx_push, m_fnma(py, ry, g.hy * fabs(ry)));
-  if (three_d) dx_push = m_min(dx_push, m_fnma(pz, rz, g.hz * fabs(rz)));
+  if constexpr (UNITCELL) {
+    dx_push = m_min(dx_push, m_fnma_abs(px, rx));
+    if (multi_d) dx_push = m_min(dx_push, m_fnma_abs(py, ry));
+    if (three_d) dx_push = m_min(dx_push, m_fnma_abs(pz, rz));
+  } else {
+    dx_push = m_min(dx_push, m_fnma(px, rx, g.hx * fabs(rx)));
+    if (multi_d) dx_push = m_min(dx_push, m_fnma(py, ry, g.hy * fabs(ry)));
+    if (three_d) dx_push = m_min(dx_push, m_fnma(pz, rz, g.hz * fabs(rz)));
+  }
   is_absorbed = NOABS ? false : (dx_abs < dx_push) && (dx_abs < dx_sc);
   is_scattered = !is_absorbed && (dx_sc < dx_push);
   const double dx_move =
@@ -649,8 +663,40 @@ __device__ __forceinline__ unsigned cross_level(int code, unsigned dst, int sy, 
 
 // scattering.hpp:21-29 in direction space: the new unit direction (2 draws).  The azimuth's grid point by the magic
 // constant where the generator's uniforms cannot tie (Rng::kHalfOddUniforms): the same bits, a conversion pair less.
-template <bool SC = false, class Rng>
-__device__ __forceinline__ void scatter_dir(Rng &rng, double &ox, double &oy, double &oz) {
+// UNITCELL: the direction divided by the half cell widths (imc_step_cell<.., UNITCELL>), formed on the scale of the
+// polar axis, h_z.  The stream's mantissa k goes under the exponent of 2 / h_z instead of that of 1 (u52_to_double,
+// jb_rng.hpp), so xi' = 2 xi / h_z comes out of the one exact subtraction that forms xi today, and
+// mu' = xi' - 1 / h_z is the unscaled form's fma(2, xi, -1) times 1 / h_z, exact like it: two instructions, as
+// before.  (Not one: mu = 2 (1.k) - (3 - 2^-52) would need a constant with 53 bits behind the leading one.)
+// s' = 1 / h_z^2 - mu' mu', st' = sqrt(s') = st / h_z (a power of four into the reciprocal square root: half its
+// exponent out); omega'_x = st' cs, omega'_y = st' sn where the widths are equal (EQUALH), else st' first goes to
+// the x and y scales by two exact multiplications with powers of two.
+struct UnitScale {
+  int xi_exp;     // high word of 2 / h_z: the exponent the mantissa goes under
+  double xi_off;  // (1 - 2^-53) 2 / h_z
+  double one;     // 1 / h_z
+  double s0;      // 1 / h_z^2
+  double kx, ky;  // h_z / h_x, h_z / h_y
+};
+template <bool SC = false, bool UNITCELL = false, bool EQUALH = true, class Rng>
+__device__ __forceinline__ void scatter_dir(Rng &rng, double &ox, double &oy, double &oz,
+                                            const UnitScale &us = UnitScale{}) {
+  if constexpr (UNITCELL) {
+    static_assert(Rng::kHalfOddUniforms, "the mantissa form is the linear congruential stream's");
+    uint64_t k1;
+    double xi2;
+    rng.drand2_mant(k1, xi2);
+    const double xi =
+        __longlong_as_double((long long)(((uint64_t)(uint32_t)us.xi_exp << 32) | k1)) - us.xi_off;
+    const double mu = xi - us.one;
+    const double st = m_sqrt_lean(us.s0 - mu * mu);
+    double sn, cs;
+    m_sincos2pi<SC, !JB_IMC_PARENT_AZIMUTH>(xi2, sn, cs);
+    ox = (EQUALH ? st : st * us.kx) * cs;
+    oy = (EQUALH ? st : st * us.ky) * sn;
+    oz = mu;
+    return;
+  }
   double xi1, xi2;
   rng.drand2(xi1, xi2);
   const double mu = fma(2.0, xi1, -1.0);

@@ -112,6 +112,15 @@ struct LcgRng {
     u1 = u52_to_double(s1 >> 12);
     u2 = u52_to_double(s >> 12);
   }
+  // drand2 with the first draw left as its 52-bit mantissa k: u1 = (k + 1/2) 2^-52 for a caller that puts the bits
+  // under an exponent of its own (scatter_dir<.., UNITCELL>, jb_physics.hpp); the same states
+  __device__ __forceinline__ void drand2_mant(uint64_t &k1, double &u2) {
+    constexpr uint64_t kMul2 = kLcgMul * kLcgMul, kInc2 = (kLcgMul + 1ull) * kLcgInc;
+    const uint64_t s1 = s * kLcgMul + kLcgInc;
+    s = s * kMul2 + kInc2;
+    k1 = s1 >> 12;
+    u2 = u52_to_double(s >> 12);
+  }
   // consume one draw whose value cannot influence the result
   __device__ __forceinline__ void skip() { s = s * kLcgMul + kLcgInc; }
   // ... and two (one multiply-add by the constants of two steps: the same state)

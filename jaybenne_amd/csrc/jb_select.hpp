@@ -29,6 +29,9 @@ struct TransportInputs {
   bool noabs = false;           // kappa_a == 0
   // the mesh geometry (jb_mesh)
   bool exact_geom = false, cell_ok = false, uniform_geom = false;
+  bool equal_h = false;         // the active cell widths of block 0 are equal
+  // the library: false in a build without k_imc_cell's unit-cell form (-DJB_IMC_PARENT_COORDS)
+  bool unit_cell_form = true;
   // the context
   bool lean_arith = true, no_imc_cell = false;
   int coop_gather = -1;         // JB_COOP_GATHER
@@ -49,6 +52,8 @@ struct TransportPlan {
   bool exact = false, lean = false;   // k_transport
   bool noabs = false;              // k_imc_cell, k_hybrid
   bool uniform = false;            // k_imc_cell
+  // k_imc_cell: position and direction in units of the half cell width (UNITCELL); every active width equal (EQUALH)
+  bool unit_cell = false, equal_h = false;
   int gather = 0;                  // k_ddmc_all
   bool lcodes = false;             // k_ddmc_q
   int mode = 0;                    // k_hybrid: 0 exact arithmetic, 1 lean, 2 lean on exact geometry, 3 lean, cell-local
@@ -127,6 +132,11 @@ inline TransportPlan select_transport(const TransportInputs &in) {
     p.family = Family::k_imc_cell;
     p.noabs = in.noabs;
     p.uniform = in.uniform_geom;
+    // ... in units of the half cell width where that is one wave-uniform power of two per axis (every stepdiff
+    // deck: the scaling is exact, the results are the unscaled form's bit for bit, jb_kernel_imc.hpp); other
+    // uniform widths (1/24), blocks of several sizes keep the form above.  The name below does not say which.
+    p.unit_cell = in.unit_cell_form && in.uniform_geom && in.exact_geom;
+    p.equal_h = p.unit_cell && in.equal_h;
     return p;
   }
   // gray opacity with kappa = 0 (opacity_model = none): sigma_a = rho * 0 in every cell
