@@ -2,7 +2,7 @@
 // what the reference's src/mcblock does around the jaybenne package, on one GPU, with no Python
 // and no PyTorch in the process.
 //
-//   mcblock_amd -i <deck> [block/key=value ...] [--tolerance X] [--dump file] [--ledger file] [--moments file] [--comb-history file]
+//   mcblock_amd -i <deck> [block/key=value ...] [--tolerance X] [--dump file] [--ledger file] [--moments file] [--spectrum file] [--comb-history file]
 //
 // Input deck syntax and the trailing overrides are Parthenon's (reference inputs/*.in; the
 // regression harness tst/regression_test.py:85-145 rewrites decks the same way).  It sets up the
@@ -187,7 +187,7 @@ static uint64_t Morton(const int l[3], int bits) {
 
 int main(int argc, char **argv) {
   try {
-    std::string deck, dump, ledger_path, moments_path, comb_path;
+    std::string deck, dump, ledger_path, moments_path, spectrum_path, comb_path;
     double tolerance = -1.0;
     std::vector<std::string> overrides;
     for (int a = 1; a < argc; ++a) {
@@ -197,11 +197,12 @@ int main(int argc, char **argv) {
       else if (s == "--dump" && a + 1 < argc) dump = argv[++a];
       else if (s == "--ledger" && a + 1 < argc) ledger_path = argv[++a];
       else if (s == "--moments" && a + 1 < argc) moments_path = argv[++a];
+      else if (s == "--spectrum" && a + 1 < argc) spectrum_path = argv[++a];
       else if (s == "--comb-history" && a + 1 < argc) comb_path = argv[++a];
       else overrides.push_back(s);
     }
     if (deck.empty()) {
-      std::fprintf(stderr, "usage: mcblock_amd -i deck [block/key=value ...] [--tolerance X] [--dump file] [--ledger file] [--moments file] [--comb-history file]\n");
+      std::fprintf(stderr, "usage: mcblock_amd -i deck [block/key=value ...] [--tolerance X] [--dump file] [--ledger file] [--moments file] [--spectrum file] [--comb-history file]\n");
       return 2;
     }
     ParameterInput pin;
@@ -632,6 +633,17 @@ int main(int argc, char **argv) {
     std::FILE *moments_file = nullptr;
     if (!moments_path.empty() && !(moments_file = std::fopen(moments_path.c_str(), "w")))
       throw std::runtime_error("cannot write " + moments_path);
+    // --spectrum FILE (or <jaybenne_amd> spectrum = true: spectrum.jsonl) with <jaybenne_amd> spectrum_edges = e0, e1,
+    // ..: after every cycle one JSON line with the report of EvaluateRadiationSpectrum, the edges and the domain
+    // integral of every bin; off: the keys do nothing and none of its kernels runs
+    if (spectrum_path.empty() && pin.GetOrAddBoolean("jaybenne_amd", "spectrum", false)) spectrum_path = "spectrum.jsonl";
+    std::FILE *spectrum_file = nullptr;
+    std::vector<double> spectrum_edges;
+    if (!spectrum_path.empty()) {
+      spectrum_edges = jb::ParseSpectrumEdges(pin.GetOrAddString("jaybenne_amd", "spectrum_edges", ""));
+      if (!(spectrum_file = std::fopen(spectrum_path.c_str(), "w")))
+        throw std::runtime_error("cannot write " + spectrum_path);
+    }
     // --comb-history FILE: one JSON line per cycle whose census comb changed the swarm
     std::FILE *comb_file = nullptr;
     if (!comb_path.empty() && !(comb_file = std::fopen(comb_path.c_str(), "w")))
@@ -682,9 +694,17 @@ int main(int argc, char **argv) {
         std::fprintf(moments_file, "%s\n", jb::MomentsJson(md.cycle, time, rep, I).c_str());
         std::printf(" eddington=[%.4f, %.4f, %.4f]", I.eddington[0], I.eddington[1], I.eddington[2]);
       }
+      if (spectrum_file) {
+        jb_spectrum_report rep{};
+        const std::vector<double> spec = jb::EvaluateRadiationSpectrum(&md, spectrum_edges, &rep);
+        const std::vector<double> integ =
+            jb::IntegrateSpectrum(spec, (int)spectrum_edges.size() + 1, nb, (int64_t)ncell, dx.data());
+        std::fprintf(spectrum_file, "%s\n", jb::SpectrumJson(md.cycle, time, rep, spectrum_edges, integ).c_str());
+      }
       std::printf("\n");
     }
     if (ledger_file) std::fclose(ledger_file);
+    if (spectrum_file) std::fclose(spectrum_file);
     if (moments_file) std::fclose(moments_file);
     if (comb_file) std::fclose(comb_file);
     if (jb::LedgerEnabled(&md)) {   // totals by face

@@ -661,6 +661,63 @@ jb_status jb_evaluate_radiation_moments(jb_context *ctx, jb_mesh *mesh, const jb
 jb_status jb_evaluate_radiation_moments_host(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
                                              double *out_host, jb_moments_report *report /* or NULL */);
 
+/* ---- radiation spectrum: per-cell energy density of the census in frequency groups
+ * (jaybenne_amd/csrc/jb_kernel_spectrum.hpp).  Every photon carries its energy e -- both sources draw it from a
+ * Planck law, and under EPBremss it is the frequency the absorption opacity is evaluated at --, and energy_tally,
+ * the moments and the ledger all integrate over it.  A sibling of jb_evaluate_radiation_moments, called between
+ * two cycles, with that call's rules wherever nothing else is said here.
+ * edges_host[0 .. ngroups]: ngroups + 1 finite, strictly increasing doubles on the host (read before the call returns),
+ * 1 <= ngroups <= JB_SPECTRUM_MAX_GROUPS.  There are NB = ngroups + 2 bins, and
+ *     THE BIN OF A PHOTON IS THE NUMBER OF EDGES j WITH edges[j] <= e.
+ * Bin 0 is below the first edge -- and takes an e that is NaN, negative, zero or -inf: every comparison is false --,
+ * bins g = 1 .. ngroups are the groups [edges[g - 1], edges[g]), bin ngroups + 1 is at or above the last edge, +inf
+ * included.  The rule is applied literally, by comparisons, with no logarithm or reciprocal bin width: edges are
+ * data, and a photon that sits on an edge lands in the same bin in every implementation.
+ * out_dev: a caller-owned device array [NB][nblocks][ncell] (jb_spectrum_words doubles), interior cells in (k, j, i)
+ * order, blocks in the mesh's resident order:
+ *     out[bin][block][cell] = (sum of w over the cell's ACTIVE photons in that bin) / dv,   dv = (dx0 dx1) dx2,
+ * the division one rounding.  Which photons count (the sort key's cell) and which are skipped is the moments'
+ * rule; cells of halo copies and empty cells get zeros: every word of out_dev is written.
+ * Order of summation: for each bin the moments' order over the positions of the cell's run -- the run is cut into
+ * chunks of 4096 slots counted from its head; in a chunk "lane" l = 0 .. 63 starts from +0.0 and adds the elements
+ * l, l + 64, l + 128, .. in rising order; the 64 lane sums are joined by  for d in 32, 16, 8, 4, 2, 1: s[l] = s[l] +
+ * s[l + d] for l < d;  the run's sum is the first chunk's sum with the further chunks' sums added in chunk order.
+ * A photon's addend to its own bin is w; for every other bin the photon is skipped -- a lane sum that starts from
+ * +0.0 is never -0.0, so skipping equals adding +0.0, bit for bit.  No floating-point atomics.  Consequences:
+ * with edges = {4.9e-324, DBL_MAX} and every e positive and finite, bin 1 is JB_MOM_E of
+ * jb_evaluate_radiation_moments on the same swarm bit for bit; the result does not depend on the launch geometry,
+ * on the lanes per cell or on where the cell lies in the swarm; under JB_CELL_ORDER_BY_ID it does not depend on the
+ * slot order or on the number of ranks the blocks are dealt to (a cell's photons on one rank: a block partition; the
+ * sum of several ranks' arrays on a replicated mesh is another order of summation).
+ * As jb_evaluate_radiation_moments: the question "in order already?" and the sort under either cell order
+ * (report->sorted; a sort for jb_defrag_policy); ONE stream synchronisation, none for n = 0, ONE more when report
+ * is not NULL (the edges travel as a kernel argument: no copy to wait for); a comb plan not yet applied is discarded;
+ * energy_tally, energy_delta, open deposit accumulators and everything a photon carries are left as they were,
+ * the slots aside, which the sort permutes; the sort's limits.  Scratch: what the sort takes, plus 16 NB bytes per
+ * 4096 photons.
+ * report: n_counted .. sorted as jb_moments_report's; n_below, n_above: the counted photons in bin 0 and in bin
+ * ngroups + 1.
+ * JB_ERR_INVALID: a null ctx, mesh, swarm, edges_host or out_dev, the sort's limits, ngroups outside
+ * [1, JB_SPECTRUM_MAX_GROUPS], an edge that is not finite or not above the one before it -- then nothing is
+ * launched and nothing written; JB_ERR_HIP with the swarm as it was when the scratch cannot be allocated.  n = 0
+ * is valid and writes zeros.  Opens the trace range "Jaybenne::EvaluateRadiationSpectrum". */
+#define JB_SPECTRUM_MAX_GROUPS 64
+typedef struct jb_spectrum_report {
+  int64_t n_counted, n_skipped;      /* slots of [0, n) summed / not summed */
+  int64_t cells_nonempty, longest_run;
+  int64_t n_below, n_above;          /* counted photons in bin 0 / bin ngroups + 1 */
+  int32_t sorted, pad;               /* 1: the call had to sort */
+} jb_spectrum_report;
+int64_t jb_spectrum_words(const jb_mesh *mesh, int ngroups);   /* (ngroups + 2) * nblocks * ncell; 0: bad ngroups */
+jb_status jb_evaluate_radiation_spectrum(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
+                                         const double *edges_host, int ngroups, double *out_dev,
+                                         jb_spectrum_report *report /* or NULL */);
+/* The same into a HOST array of jb_spectrum_words doubles, through a device array the context keeps
+ * (jb_release_scratch returns it); synchronises the stream at the end. */
+jb_status jb_evaluate_radiation_spectrum_host(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
+                                              const double *edges_host, int ngroups, double *out_host,
+                                              jb_spectrum_report *report /* or NULL */);
+
 /* MeshSend / MeshReceive (jaybenne.cpp:36-61) for the inter-rank part: OUTGOING particles are
  * among [first,last) are copied into fixed-size records (JB_RECORD_WORDS x 8 bytes), ordered by
  * destination rank, and their slots are re-marked JB_ST_ABSORBED-like holes (status

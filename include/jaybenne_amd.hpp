@@ -18,8 +18,10 @@
 #ifndef JAYBENNE_AMD_HPP_
 #define JAYBENNE_AMD_HPP_
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cmath>
 #include <functional>
 #include <limits>
@@ -910,6 +912,101 @@ inline std::string MomentsJson(uint64_t cycle, double time, const jb_moments_rep
       (long long)r.longest_run, (int)r.sorted, I.n, I.e, I.w2, I.f[0], I.f[1], I.f[2], I.q[0], I.q[1], I.q[2], I.q[3],
       I.q[4], I.q[5], I.eddington[0], I.eddington[1], I.eddington[2]);
   return std::string(buf, n > 0 ? (size_t)n : 0);
+}
+
+// ---- radiation spectrum (jaybenne_amd.h: jb_evaluate_radiation_spectrum): only when a host asks ------------
+// Per-cell energy density of the census in the ngroups + 2 bins of edges.size() - 1 frequency groups as a host array
+// [ngroups + 2][nblocks][ncell] (interior cells in (k, j, i) order; zeros in halo copies).  Sorts the swarm by
+// (block, cell) when it is not in that order.
+inline std::vector<double> EvaluateRadiationSpectrum(MeshData *md, const std::vector<double> &edges,
+                                                     jb_spectrum_report *report = nullptr) {
+  const int ngroups = (int)edges.size() - 1;
+  std::vector<double> out((size_t)jb_spectrum_words(md->mesh(), ngroups));
+  Check(jb_evaluate_radiation_spectrum_host(md->ctx(), md->mesh(), &md->swarm, edges.data(), ngroups, out.data(), report));
+  return out;
+}
+// `spectrum_edges = e0, e1, ..` of a deck or a command line: a comma-separated list of decimal numbers; blanks
+// around a number and empty items are ignored.  A number is  [+-] digits [. digits] | [+-] . digits,  then
+// optionally  e|E [+-] digits  -- one grammar in every host (`python -m jaybenne_amd` holds its list to the same
+// before float()), so that no text is a number to one host and an error to another: no hex floats, no inf or nan,
+// no digit separators.  The value is strtod's, correctly rounded.  Anything else throws, naming the item.
+inline bool IsDecimalNumber(const std::string &t) {
+  size_t q = 0;
+  auto digits = [&] {
+    const size_t q0 = q;
+    while (q < t.size() && t[q] >= '0' && t[q] <= '9') ++q;
+    return q - q0;
+  };
+  if (q < t.size() && (t[q] == '+' || t[q] == '-')) ++q;
+  size_t mant = digits();
+  if (q < t.size() && t[q] == '.') {
+    ++q;
+    mant += digits();
+  }
+  if (mant == 0) return false;
+  if (q < t.size() && (t[q] == 'e' || t[q] == 'E')) {
+    ++q;
+    if (q < t.size() && (t[q] == '+' || t[q] == '-')) ++q;
+    if (digits() == 0) return false;
+  }
+  return q == t.size();
+}
+inline std::vector<double> ParseSpectrumEdges(const std::string &text) {
+  std::vector<double> edges;
+  size_t at = 0;
+  while (at <= text.size()) {
+    const size_t comma = std::min(text.find(',', at), text.size());
+    std::string item = text.substr(at, comma - at);
+    const size_t first = item.find_first_not_of(" \t");
+    if (first != std::string::npos) {
+      item = item.substr(first, item.find_last_not_of(" \t") - first + 1);
+      if (!IsDecimalNumber(item)) throw std::runtime_error("spectrum_edges: '" + item + "' is not a decimal number");
+      edges.push_back(std::strtod(item.c_str(), nullptr));
+    }
+    at = comma + 1;
+  }
+  if (edges.size() < 2 || edges.size() > JB_SPECTRUM_MAX_GROUPS + 1)
+    throw std::runtime_error("spectrum_edges: 2 .. 65 comma-separated edges are needed");
+  return edges;
+}
+// The domain integrals a command-line host prints per cycle: sum over cells of out[bin] dv for every bin, summed
+// sequentially in (block, cell) order, as IntegrateMoments does.
+inline std::vector<double> IntegrateSpectrum(const std::vector<double> &s, int nbins, int nblocks, int64_t ncell,
+                                             const double *blk_dx) {
+  std::vector<double> integ((size_t)nbins, 0.0);
+  for (int bin = 0; bin < nbins; ++bin) {
+    double acc = 0.0;
+    for (int b = 0; b < nblocks; ++b) {
+      const double dv = (blk_dx[3 * b] * blk_dx[3 * b + 1]) * blk_dx[3 * b + 2];
+      const double *v = s.data() + ((size_t)bin * (size_t)nblocks + (size_t)b) * (size_t)ncell;
+      for (int64_t q = 0; q < ncell; ++q) {
+        const double t = v[q] * dv;   // (its own statement: rounded before it is added)
+        acc += t;
+      }
+    }
+    integ[(size_t)bin] = acc;
+  }
+  return integ;
+}
+// one cycle's line of `--spectrum FILE` (the keys and digits of `python -m jaybenne_amd --spectrum`)
+inline std::string SpectrumJson(uint64_t cycle, double time, const jb_spectrum_report &r, const std::vector<double> &edges,
+                                const std::vector<double> &integ) {
+  char buf[512];
+  auto list = [&buf](const std::vector<double> &v) {
+    std::string s = "[";
+    for (size_t q = 0; q < v.size(); ++q) {
+      std::snprintf(buf, sizeof buf, "%s%.17g", q ? ", " : "", v[q]);
+      s += buf;
+    }
+    return s + "]";
+  };
+  std::snprintf(buf, sizeof buf,
+                "{\"cycle\": %lld, \"time\": %.17g, \"n_counted\": %lld, \"n_skipped\": %lld, \"cells_nonempty\": %lld, "
+                "\"longest_run\": %lld, \"n_below\": %lld, \"n_above\": %lld, \"sorted\": %d, \"ngroups\": %d, ",
+                (long long)cycle, time, (long long)r.n_counted, (long long)r.n_skipped, (long long)r.cells_nonempty,
+                (long long)r.longest_run, (long long)r.n_below, (long long)r.n_above, (int)r.sorted, (int)edges.size() - 1);
+  const std::string head = buf;
+  return head + "\"edges\": " + list(edges) + ", \"e\": " + list(integ) + "}";
 }
 
 // ---- energy ledger (jaybenne_amd.h: jb_ledger_*): off by default ----------------------------------

@@ -63,6 +63,55 @@ def moments_json(cycle: int, t: float, report: dict, integ: dict) -> str:
             f'"eddington": {lst(integ["eddington"])}' + "}")
 
 
+_DECIMAL = None
+
+
+def parse_spectrum_edges(text: str) -> list:
+    """``spectrum_edges = e0, e1, ..`` of a deck or a command line: a comma-separated list of decimal numbers; blanks
+    around a number and empty items are ignored.  A number is ``[+-] digits [. digits] | [+-] . digits``, then
+    optionally ``e|E [+-] digits`` -- the grammar of include/jaybenne_amd.hpp: ParseSpectrumEdges, narrower than
+    ``float`` (no ``1_0``, no ``inf`` or ``nan``) and than strtod (no hex floats), so that no text is a number to one
+    host and an error to the other.  The value is ``float``'s, correctly rounded as strtod's.  Anything else, or fewer
+    than 2 or more than 65 numbers, raises ValueError with the words examples/mcblock_amd uses."""
+    global _DECIMAL
+    if _DECIMAL is None:
+        import re
+        _DECIMAL = re.compile(r"[+-]?(?:[0-9]+(?:\.[0-9]*)?|\.[0-9]+)(?:[eE][+-]?[0-9]+)?", re.ASCII)
+    edges = []
+    for item in text.split(","):
+        item = item.strip(" \t")
+        if not item:
+            continue
+        if not _DECIMAL.fullmatch(item):
+            raise ValueError(f"spectrum_edges: '{item}' is not a decimal number")
+        edges.append(float(item))
+    if not 2 <= len(edges) <= 65:
+        raise ValueError("spectrum_edges: 2 .. 65 comma-separated edges are needed")
+    return edges
+
+
+def spectrum_integrals(spec: np.ndarray, blk_dx: np.ndarray) -> list:
+    """The domain integrals of the spectrum ``[NB, nblocks, ...]`` (``--spectrum FILE``): sum over cells of out[bin] dv
+    for every bin, summed sequentially in (block, cell) order -- as include/jaybenne_amd.hpp: IntegrateSpectrum."""
+    nb = spec.shape[1]
+    dv = (blk_dx[:nb, 0] * blk_dx[:nb, 1]) * blk_dx[:nb, 2]
+    out = []
+    for b in range(spec.shape[0]):
+        v = (spec[b].reshape(nb, -1) * dv[:, None]).reshape(-1)
+        out.append(float(np.add.accumulate(v)[-1]) if v.size else 0.0)        # (accumulate: one by one, in order)
+    return out
+
+
+def spectrum_json(cycle: int, t: float, report: dict, edges, integ) -> str:
+    """One cycle's line of ``--spectrum FILE`` (examples/mcblock_amd writes the same characters)"""
+    g = lambda x: "%.17g" % x                           # noqa: E731
+    lst = lambda xs: "[" + ", ".join(g(x) for x in xs) + "]"      # noqa: E731
+    return ("{" + f'"cycle": {int(cycle)}, "time": {g(t)}, "n_counted": {report["n_counted"]}, '
+            f'"n_skipped": {report["n_skipped"]}, "cells_nonempty": {report["cells_nonempty"]}, '
+            f'"longest_run": {report["longest_run"]}, "n_below": {report["n_below"]}, "n_above": {report["n_above"]}, '
+            f'"sorted": {report["sorted"]}, "ngroups": {len(edges) - 1}, "edges": {lst(edges)}, "e": {lst(integ)}' + "}")
+
+
 def comb_json(rec: dict) -> str:
     """One combed cycle's line of ``--comb-history FILE`` (examples/mcblock_amd writes the same characters: %.17g
     restores a float's bits); the global comb's keys only for its records."""
@@ -100,6 +149,10 @@ def main(argv=None) -> int:
                     help="after every cycle one JSON line to FILE: the report of EvaluateRadiationMoments and the "
                          "domain integrals of count, energy, flux and second-moment tensor, with the Eddington "
                          "factors (the deck key <jaybenne_amd> moments = true: to moments.jsonl)")
+    ap.add_argument("--spectrum", default=None, metavar="FILE",
+                    help="after every cycle one JSON line to FILE: the report of EvaluateRadiationSpectrum, the edges "
+                         "(deck key <jaybenne_amd> spectrum_edges = e0, e1, ..) and the domain integral of the census "
+                         "energy in every bin (the deck key <jaybenne_amd> spectrum = true: to spectrum.jsonl)")
     ap.add_argument("--comb-history", default=None, metavar="FILE",
                     help="one JSON line to FILE per cycle whose census comb (census_per_cell_max or "
                          "census_total_target) changed the swarm")
@@ -125,6 +178,15 @@ def main(argv=None) -> int:
     ledger_file = open(args.ledger, "w") if args.ledger else None
     moments_path = args.moments or ("moments.jsonl" if pin.GetOrAddBoolean("jaybenne_amd", "moments", False) else None)
     moments_file = open(moments_path, "w") if moments_path else None
+    spectrum_path = args.spectrum or ("spectrum.jsonl" if pin.GetOrAddBoolean("jaybenne_amd", "spectrum", False) else None)
+    spectrum_file, spectrum_edges = None, []
+    if spectrum_path:
+        try:
+            spectrum_edges = parse_spectrum_edges(pin.GetOrAddString("jaybenne_amd", "spectrum_edges", ""))
+        except ValueError as e:                      # (examples/mcblock_amd: the same words, the same exit code)
+            print(f"python -m jaybenne_amd: {e}", file=sys.stderr)
+            return 2
+        spectrum_file = open(spectrum_path, "w")
     comb_file = open(args.comb_history, "w") if args.comb_history else None
     print(f"problem {drv.mcb.problem_id}: {drv.mesh.ndim}-D, {drv.mesh.nblocks} meshblocks, "
           f"levels {sorted(set(drv.mesh.blk_level.tolist()))}, {drv.md.n} photons")
@@ -157,6 +219,10 @@ def main(argv=None) -> int:
                                           drv.pkg.Param("speed_of_light"))
                 moments_file.write(moments_json(drv.md.cycle, drv.time, rep, integ) + "\n")
                 line += " eddington=[" + ", ".join(f"{e:.4f}" for e in integ["eddington"]) + "]"
+            if spectrum_file is not None:
+                spec, rep = drv.jb.EvaluateRadiationSpectrum(drv.md, spectrum_edges)
+                integ = spectrum_integrals(spec.cpu().numpy(), np.asarray(drv.mesh.blk_dx)[drv.md.resident_gids])
+                spectrum_file.write(spectrum_json(drv.md.cycle, drv.time, rep, spectrum_edges, integ) + "\n")
             print(line)
     except JaybenneError as e:
         if not (checked and e.status == JB_ERR_INVARIANT):
@@ -167,6 +233,8 @@ def main(argv=None) -> int:
     print(f"walltime used = {time.perf_counter() - t0:.2f} s")
     if moments_file is not None:
         moments_file.close()
+    if spectrum_file is not None:
+        spectrum_file.close()
     if comb_file is not None:
         comb_file.close()
     if ledger_file is not None:

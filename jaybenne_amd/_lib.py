@@ -225,6 +225,19 @@ class MomentsReport(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
 
 
+# jb_spectrum_report (include/jaybenne_amd.h): radiation spectrum
+JB_SPECTRUM_MAX_GROUPS = 64
+
+
+class SpectrumReport(C.Structure):
+    _fields_ = [("n_counted", C.c_int64), ("n_skipped", C.c_int64), ("cells_nonempty", C.c_int64),
+                ("longest_run", C.c_int64), ("n_below", C.c_int64), ("n_above", C.c_int64), ("sorted", C.c_int32),
+                ("pad", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
 # jb_deposit_stats (include/jaybenne_amd.h): the counts of the last close of exact deposition
 class DepositStats(C.Structure):
     _fields_ = [("n_absorbed_addends", C.c_int64), ("n_census_addends", C.c_int64), ("n_truncated", C.c_int64),
@@ -298,6 +311,11 @@ PROTOTYPES = {
     "jb_moments_words": (_i64, [_vp]),
     "jb_evaluate_radiation_moments": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, C.POINTER(MomentsReport)]),
     "jb_evaluate_radiation_moments_host": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, C.POINTER(MomentsReport)]),
+    "jb_spectrum_words": (_i64, [_vp, _int]),
+    "jb_evaluate_radiation_spectrum": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, _int, _vp,
+                                              C.POINTER(SpectrumReport)]),
+    "jb_evaluate_radiation_spectrum_host": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, _int, _vp,
+                                                   C.POINTER(SpectrumReport)]),
     "jb_defrag_policy": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, C.c_int32, C.POINTER(C.c_int32)]),
     "jb_pack_outgoing": (_int, [_vp, _vp, C.POINTER(SwarmView), _i64, _i64, _int, _vp, _i64, _vp]),
     "jb_unpack_incoming": (_int, [_vp, _vp, C.POINTER(SwarmView), _vp, _i64]),

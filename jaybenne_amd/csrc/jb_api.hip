@@ -32,6 +32,7 @@
 #include "jb_kernel_tilt.hpp"
 #include "jb_kernel_salloc.hpp"
 #include "jb_kernel_moments.hpp"
+#include "jb_kernel_spectrum.hpp"
 #include "jb_select.hpp"
 
 using namespace jb;
@@ -131,6 +132,8 @@ struct jb_context {
   long long min_records = 0;  // JB_HANDOFF_MIN_RECORDS at jb_initialize: first size of those record buffers (tests)
   // jb_evaluate_radiation_moments_host: the device array the fields pass through
   DevBuf moments;
+  // jb_evaluate_radiation_spectrum_host: the device array the bins pass through
+  DevBuf spectrum;
   // arithmetic of the gray IMC tracking step: lean (default) or exact (JB_EXACT_ARITH=1 in the
   // environment at jb_initialize, or jb_set_arithmetic)
   bool lean_arith = true;
@@ -2613,9 +2616,54 @@ static MomScratch mom_scratch(const jb_context *ctx, const MomLayout &L) {
   return {sort_scratch(ctx, L.sort), scratch_at<double>(ctx, L.part), scratch_at<unsigned long long>(ctx, L.stats),
           scratch_at<unsigned>(ctx, L.flag)};
 }
+// The first part of a moments or a spectrum call: the swarm into (block, cell) order and the cells' bounds into
+// p.hist.  In order already?  As jb_comb_census_plan asks: key order under JB_CELL_ORDER_ANY, the canonical order --
+// whose sort makes that test itself -- under JB_CELL_ORDER_BY_ID; if not, the sort (*unsorted = 1; for
+// jb_defrag_policy that is a sort, as a comb plan that sorted is).  Synchronises the stream once, not at all for
+// n = 0.  flag: a word of scratch.
+static jb_status cells_in_order(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm, const CellKeys &k,
+                                const SortLayout &sort, const SortScratch &p, unsigned *flag, unsigned *unsorted_out) {
+  const long long n = swarm->n;
+  const DevMesh &M = mesh->dm;
+  const DevSwarm S = dev_swarm(swarm);
+  const bool by_id = sort.by_id;
+  jb_status st;
+  unsigned unsorted = 0u;
+  if (n > 0 && by_id) {
+    int moved = 0;
+    st = order_sort(ctx, mesh, swarm, k.nkeys, sort, &moved);
+    if (st != JB_COMPLETE) return st;
+    unsorted = moved ? 1u : 0u;
+  } else if (n > 0) {
+    // (one pass makes the keys and the histogram the cells' bounds come from; a swarm in order needs no second)
+    JB_HIP(hipMemsetAsync(flag, 0, sizeof(unsigned), ctx->stream));
+    if ((st = count_cells(ctx, M, S, n, k, p)) != JB_COMPLETE) return st;
+    hipLaunchKernelGGL(k_comb_unsorted, dim3(grid_for(ctx, n)), dim3(kBlock), 0, ctx->stream, (const unsigned *)p.key, n, flag);
+    JB_HIP(hipGetLastError());
+    JB_HIP(hipMemcpyAsync(&unsorted, flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    JB_HIP(hipStreamSynchronize(ctx->stream));
+    if (unsorted) {
+      st = jb_defrag_particles(ctx, mesh, swarm);
+      if (st != JB_COMPLETE) return st;
+    }
+  }
+  if (unsorted) defrag_schedule_restart(ctx);
+  // the cells' bounds: the histogram of the keys of the swarm as it lies now, and its scan (what a move left in
+  // the histogram's place are the cells' ends, not their starts)
+  const bool counted = n > 0 && !by_id && !unsorted;   // the histogram of the order test stands
+  if (n > 0) {
+    if (!counted && (st = count_cells(ctx, M, S, n, k, p)) != JB_COMPLETE) return st;
+    scan_u32(ctx, p.hist, k.nbins, p.sums);
+  } else {   // (every cell is empty)
+    JB_HIP(hipMemsetAsync(p.hist, 0, sizeof(unsigned) * (size_t)k.nbins, ctx->stream));
+  }
+  *unsorted_out = unsorted;
+  return JB_COMPLETE;
+}
+
 // lanes per cell of k_mom_cells: the power of two that holds about twice the mean run and two more
-static int mom_group(long long n, long long cells) {
-  if (const char *e = getenv("JB_MOMENTS_GROUP")) {
+static int mom_group(long long n, long long cells, const char *aid = "JB_MOMENTS_GROUP") {
+  if (const char *e = getenv(aid)) {
     const int g = atoi(e);
     if (g >= 1 && g <= 64 && (g & (g - 1)) == 0) return g;
   }
@@ -2651,39 +2699,9 @@ extern "C" jb_status jb_evaluate_radiation_moments(jb_context *ctx, jb_mesh *mes
   ctx->comb.valid = ctx->weigh.valid = false;   // (a comb plan not yet applied lived in this memory)
   const MomScratch m = mom_scratch(ctx, L);
   const DevSwarm S = dev_swarm(swarm);
-  const int gn = grid_for(ctx, n);
-  // In order already?  As jb_comb_census_plan asks: key order under JB_CELL_ORDER_ANY, the canonical order -- whose
-  // sort makes that test itself -- under JB_CELL_ORDER_BY_ID.
   unsigned unsorted = 0u;
-  if (n > 0 && by_id) {
-    int moved = 0;
-    st = order_sort(ctx, mesh, swarm, nkeys, L.sort, &moved);
-    if (st != JB_COMPLETE) return st;
-    unsorted = moved ? 1u : 0u;
-  } else if (n > 0) {
-    // (one pass makes the keys and the histogram the cells' bounds come from; a swarm in order needs no second)
-    JB_HIP(hipMemsetAsync(m.flag, 0, sizeof(unsigned), ctx->stream));
-    if ((st = count_cells(ctx, M, S, n, k, m)) != JB_COMPLETE) return st;
-    hipLaunchKernelGGL(k_comb_unsorted, dim3(gn), dim3(kBlock), 0, ctx->stream, (const unsigned *)m.key, n, m.flag);
-    JB_HIP(hipGetLastError());
-    JB_HIP(hipMemcpyAsync(&unsorted, m.flag, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    JB_HIP(hipStreamSynchronize(ctx->stream));
-    if (unsorted) {
-      st = jb_defrag_particles(ctx, mesh, swarm);
-      if (st != JB_COMPLETE) return st;
-    }
-  }
-  if (unsorted) defrag_schedule_restart(ctx);   // for the policy this is a sort, as a comb plan that sorted is
-  // the cells' bounds: the histogram of the keys of the swarm as it lies now, and its scan (what a move left in
-  // the histogram's place are the cells' ends, not their starts)
+  if ((st = cells_in_order(ctx, mesh, swarm, k, L.sort, m, m.flag, &unsorted)) != JB_COMPLETE) return st;
   JB_HIP(hipMemsetAsync(m.stats, 0, sizeof(unsigned long long) * MS_N, ctx->stream));
-  const bool counted = n > 0 && !by_id && !unsorted;   // the histogram of the order test stands
-  if (n > 0) {
-    if (!counted && (st = count_cells(ctx, M, S, n, k, m)) != JB_COMPLETE) return st;
-    scan_u32(ctx, m.hist, k.nbins, m.sums);
-  } else {   // (every cell is empty)
-    JB_HIP(hipMemsetAsync(m.hist, 0, sizeof(unsigned) * (size_t)k.nbins, ctx->stream));
-  }
   const int G = mom_group(n, cells);
   // (one workgroup per 256 slots, not a grid capped to the chip: chunk heads lie 64 waves apart in a long run, and
   // a strided walk would hand all of them to the same few waves; the hardware deals workgroups out as others end)
@@ -2719,6 +2737,110 @@ extern "C" jb_status jb_evaluate_radiation_moments_host(jb_context *ctx, jb_mesh
   st = jb_evaluate_radiation_moments(ctx, mesh, swarm, (double *)ctx->moments.p, report);
   if (st != JB_COMPLETE) return st;
   JB_HIP(hipMemcpyAsync(out_host, ctx->moments.p, words * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  JB_HIP(hipStreamSynchronize(ctx->stream));
+  return JB_COMPLETE;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Radiation spectrum (jb_kernel_spectrum.hpp).  Its scratch lies behind the sort's (jb_scratch_layout.hpp:
+// spectrum_layout); the call is the moments' up to the kernels.
+static_assert(kSpecMaxGroups == JB_SPECTRUM_MAX_GROUPS && sizeof(jb_spectrum_report) == 56,
+              "jb_limits.hpp restates the header");
+struct SpecScratch : SortScratch {
+  double *part;
+  unsigned long long *stats;
+  unsigned *flag;
+};
+static SpecScratch spec_scratch(const jb_context *ctx, const SpecLayout &L) {
+  return {sort_scratch(ctx, L.sort), scratch_at<double>(ctx, L.part), scratch_at<unsigned long long>(ctx, L.stats),
+          scratch_at<unsigned>(ctx, L.flag)};
+}
+// ngroups + 1 finite, strictly increasing edges
+static jb_status check_edges(const double *edges, int ngroups, const char *who) {
+  if (ngroups < 1 || ngroups > JB_SPECTRUM_MAX_GROUPS)
+    return fail(JB_ERR_INVALID, "%s: ngroups = %d is not in [1, %d]", who, ngroups, JB_SPECTRUM_MAX_GROUPS);
+  if (!edges) return fail(JB_ERR_INVALID, "%s: null argument", who);
+  for (int j = 0; j <= ngroups; ++j) {
+    if (!std::isfinite(edges[j])) return fail(JB_ERR_INVALID, "%s: edge %d is not finite", who, j);
+    if (j > 0 && !(edges[j - 1] < edges[j])) return fail(JB_ERR_INVALID, "%s: edge %d is not above edge %d", who, j, j - 1);
+  }
+  return JB_COMPLETE;
+}
+
+extern "C" int64_t jb_spectrum_words(const jb_mesh *mesh, int ngroups) {
+  if (!mesh || ngroups < 1 || ngroups > JB_SPECTRUM_MAX_GROUPS) return 0;
+  return (int64_t)(ngroups + 2) * (int64_t)mesh->dm.nblocks * (int64_t)mesh->dm.ncell;
+}
+
+extern "C" jb_status jb_evaluate_radiation_spectrum(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
+                                                    const double *edges_host, int ngroups, double *out_dev,
+                                                    jb_spectrum_report *report) {
+  JB_RANGE("Jaybenne::EvaluateRadiationSpectrum");
+  if (!ctx || !mesh || !out_dev) return fail(JB_ERR_INVALID, "jb_evaluate_radiation_spectrum: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  jb_status st = check_swarm(swarm, "jb_evaluate_radiation_spectrum");
+  if (st != JB_COMPLETE) return st;
+  if ((st = check_edges(edges_host, ngroups, "jb_evaluate_radiation_spectrum")) != JB_COMPLETE) return st;
+  const long long n = swarm->n;
+  const DevMesh &M = mesh->dm;
+  const CellKeys k = cell_keys(M.nblocks, M.ntot, n);
+  if ((st = check_cell_keys(k, "jb_evaluate_radiation_spectrum")) != JB_COMPLETE) return st;
+  const long long cells = (long long)M.nblocks * M.ncell;
+  if (report) memset(report, 0, sizeof *report);
+  const SpecLayout L = spectrum_layout(n, k.nbins, order_by_id(ctx), ngroups);
+  // (all of the scratch first: the sort then finds room, and a failed allocation leaves the swarm as it was)
+  st = ensure_scratch(ctx, L.words, /*slack=*/false);
+  if (st != JB_COMPLETE) return st;
+  ctx->comb.valid = ctx->weigh.valid = false;   // (a comb plan not yet applied lived in this memory)
+  const SpecScratch m = spec_scratch(ctx, L);
+  const DevSwarm S = dev_swarm(swarm);
+  SpecEdges edges{};   // (a kernel argument by value: no copy to the device, nothing to wait for)
+  memcpy(edges.v, edges_host, sizeof(double) * (size_t)(ngroups + 1));
+  unsigned unsorted = 0u;
+  if ((st = cells_in_order(ctx, mesh, swarm, k, L.sort, m, m.flag, &unsorted)) != JB_COMPLETE) return st;
+  JB_HIP(hipMemsetAsync(m.stats, 0, sizeof(unsigned long long) * SS_N, ctx->stream));
+  const int G = mom_group(n, cells, "JB_SPECTRUM_GROUP");
+  const size_t lds = sizeof(double) * (64 * (size_t)(ngroups + 2) + (size_t)(ngroups + 1));
+  // (one workgroup -- one wave -- per 64 slots, not a grid capped to the chip: as k_mom_chunks)
+  if (n > 0)
+    hipLaunchKernelGGL(k_spec_chunks, dim3((unsigned)((n + kSpecBlock - 1) / kSpecBlock)), dim3(kSpecBlock), lds,
+                       ctx->stream, M, S, n, k.nkeys, (const unsigned *)m.key, (const unsigned *)m.hist, (unsigned)G, edges,
+                       ngroups, m.part, out_dev, m.stats);
+  const long long waves = (cells + 63) / 64, cap = (long long)ctx->num_cu * 32;
+  const unsigned gc = (unsigned)(waves < 1 ? 1 : waves < cap ? waves : cap);
+  with_int<1, 2, 4, 8, 16, 32, 64>(G, [&](auto g) {
+    hipLaunchKernelGGL(k_spec_cells<decltype(g)::value>, dim3(gc), dim3(kSpecBlock), lds, ctx->stream, M, S,
+                       (const unsigned *)m.hist, (const double *)m.part, edges, ngroups, out_dev, m.stats);
+  });
+  JB_HIP(hipGetLastError());
+  if (report) {
+    unsigned long long stats[SS_N] = {};
+    JB_HIP(hipMemcpyAsync(stats, m.stats, sizeof stats, hipMemcpyDeviceToHost, ctx->stream));
+    JB_HIP(hipStreamSynchronize(ctx->stream));
+    report->n_counted = (int64_t)stats[SS_COUNTED];
+    report->n_skipped = (int64_t)n - report->n_counted;
+    report->cells_nonempty = (int64_t)stats[SS_NONEMPTY];
+    report->longest_run = (int64_t)stats[SS_LONGEST];
+    report->n_below = (int64_t)stats[SS_BELOW];
+    report->n_above = (int64_t)stats[SS_ABOVE];
+    report->sorted = unsorted ? 1 : 0;
+  }
+  return JB_COMPLETE;
+}
+
+extern "C" jb_status jb_evaluate_radiation_spectrum_host(jb_context *ctx, jb_mesh *mesh, const jb_swarm_view *swarm,
+                                                         const double *edges_host, int ngroups, double *out_host,
+                                                         jb_spectrum_report *report) {
+  if (!ctx || !mesh || !out_host) return fail(JB_ERR_INVALID, "jb_evaluate_radiation_spectrum_host: null argument");
+  JB_HIP(hipSetDevice(ctx->device));
+  jb_status st = check_edges(edges_host, ngroups, "jb_evaluate_radiation_spectrum_host");
+  if (st != JB_COMPLETE) return st;
+  const size_t words = (size_t)jb_spectrum_words(mesh, ngroups);
+  st = dev_grow(ctx->spectrum, words * sizeof(double), "hipMalloc of the spectrum array");
+  if (st != JB_COMPLETE) return st;
+  st = jb_evaluate_radiation_spectrum(ctx, mesh, swarm, edges_host, ngroups, (double *)ctx->spectrum.p, report);
+  if (st != JB_COMPLETE) return st;
+  JB_HIP(hipMemcpyAsync(out_host, ctx->spectrum.p, words * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   JB_HIP(hipStreamSynchronize(ctx->stream));
   return JB_COMPLETE;
 }
@@ -2761,7 +2883,7 @@ extern "C" jb_status jb_release_scratch(jb_context *ctx) {
   ctx->scratch_d = nullptr;
   ctx->scratch_words = 0;
   ++ctx->scratch_gen;
-  for (DevBuf *b : {&ctx->step_send, &ctx->step_recv, &ctx->step_gather, &ctx->moments}) JB_HIP(dev_free(*b));
+  for (DevBuf *b : {&ctx->step_send, &ctx->step_recv, &ctx->step_gather, &ctx->moments, &ctx->spectrum}) JB_HIP(dev_free(*b));
   return JB_COMPLETE;
 }
 

@@ -26,5 +26,8 @@ constexpr int kScanTile = 2048;
 // one wave sums -- a run is cut into chunks of this many slots from its head (a power of two, a multiple of 64)
 constexpr int kMoments = 12;
 constexpr int kMomChunk = 4096;
+// radiation spectrum (jb_kernel_spectrum.hpp): frequency groups at the most (JB_SPECTRUM_MAX_GROUPS); a call with
+// ngroups groups has ngroups + 1 edges and ngroups + 2 bins
+constexpr int kSpecMaxGroups = 64;
 
 }  // namespace jb

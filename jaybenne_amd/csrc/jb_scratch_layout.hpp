@@ -1,9 +1,10 @@
 // jb_scratch_layout.hpp -- where the arrays of the swarm sort (jb_defrag_particles), of the census comb
-// (jb_comb_census_plan / _apply) and of the radiation moments (jb_evaluate_radiation_moments) lie in the library's
-// scratch memory: the single statement of that layout.  An array is a Span -- its first byte from the start of the
-// scratch memory, its elements and their size --; jb_api.hip turns a layout into pointers and asks it for the
-// size, so the two cannot disagree.  Pure functions of a few scalars; tests/scratch_layout_test.cpp holds every
-// offset to the arithmetic these functions replaced.  Plain C++17: no HIP include.
+// (jb_comb_census_plan / _apply), of the radiation moments (jb_evaluate_radiation_moments) and of the radiation
+// spectrum (jb_evaluate_radiation_spectrum) lie in the library's scratch memory: the single statement of that
+// layout.  An array is a Span -- its first byte from the start of the scratch memory, its elements and their size
+// --; jb_api.hip turns a layout into pointers and asks it for the size, so the two cannot disagree.  Pure functions
+// of a few scalars; tests/scratch_layout_test.cpp holds every offset to the arithmetic these functions replaced.
+// Plain C++17: no HIP include.
 #pragma once
 
 #include <cstddef>
@@ -17,6 +18,7 @@ constexpr int kSortRecWords = 16;        // 8-byte words per particle record of 
 constexpr int kCombParts = 1024;         // workgroups of k_comb_cells / k_comb_energy at the most
 constexpr int kMomSums = kMoments - 1;   // the rounded sums: components 1 .. 11 (component 0 is the count)
 enum { MS_COUNTED = 0, MS_NONEMPTY, MS_LONGEST, MS_N };   // the counts of k_mom_cells' report
+enum { SS_COUNTED = 0, SS_NONEMPTY, SS_LONGEST, SS_BELOW, SS_ABOVE, SS_N };   // ... of the spectrum kernels'
 
 struct Span {
   size_t off = 0;     // first byte, from the start of the scratch memory
@@ -156,6 +158,25 @@ inline MomLayout mom_layout(long long n, long long nbins, bool by_id) {
   m.flag = {m.stats.end(), 1, 4};
   m.words = m.flag.off / 8 + 1;
   return m;
+}
+
+// The spectrum, behind the sort: the chunks' partial sums (two places of nbins_e = ngroups + 2 doubles per
+// kMomChunk slots, as the moments'), the counts of the report, the "out of order" flag.  (The edges are a kernel
+// argument.)
+struct SpecLayout {
+  SortLayout sort;
+  Span part, stats, flag;
+  size_t words = 0;
+};
+inline SpecLayout spectrum_layout(long long n, long long nbins, bool by_id, int ngroups) {
+  SpecLayout s;
+  if (n < 0) n = 0;
+  s.sort = sort_layout(n, nbins, by_id);
+  s.part = {8 * s.sort.words, (size_t)(ngroups + 2) * 2 * (size_t)((n + kMomChunk - 1) / kMomChunk), 8};
+  s.stats = {s.part.end(), (size_t)SS_N, 8};
+  s.flag = {s.stats.end(), 1, 4};
+  s.words = s.flag.off / 8 + 1;
+  return s;
 }
 
 }  // namespace jb

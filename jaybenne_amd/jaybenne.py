@@ -274,6 +274,10 @@ class MeshData:
         # source call under "energy"
         self.source_e_total: Optional[float] = None
         self.moments_report: Optional[dict] = None
+        # radiation spectrum (EvaluateRadiationSpectrum; include/jaybenne_amd.h: jb_evaluate_radiation_spectrum): the
+        # last call's device tensor (ngroups + 2, nblocks, nx3, nx2, nx1) and report; None until a host asks
+        self.spectrum: Optional[torch.Tensor] = None
+        self.spectrum_report: Optional[dict] = None
         # exact deposition (md.deposition; include/jaybenne_amd.h: jb_set_deposition): one record per cycle, the
         # counts of its close on this rank (jb_deposit_stats) and the cycle
         self.deposit_history: list = []
@@ -882,6 +886,42 @@ def EvaluateRadiationMoments(md: MeshData):
         report["longest_run"] = int(md.moments[0].max().item()) if md.moments[0].numel() else 0
     md.moments_report = report
     return md.moments, report
+
+
+def EvaluateRadiationSpectrum(md: MeshData, edges):
+    """Per-cell energy density of the census in frequency groups (the reference has no such task;
+    include/jaybenne_amd.h: ``jb_evaluate_radiation_spectrum``).  ``edges``: ``ngroups + 1`` finite, strictly
+    increasing photon energies; a photon's bin is the number of edges ``<= e``, so bin 0 lies below the first edge and
+    bin ``ngroups + 1`` at or above the last.  Returns ``(spectrum, report)``: a device tensor of shape
+    ``(ngroups + 2, nblocks, nx3, nx2, nx1)`` over the resident blocks (zeros in halo copies), also kept as
+    ``md.spectrum``, and the call's report as a dict.  Sorts the swarm and reduces over the ranks of a replicated mesh
+    exactly as ``EvaluateRadiationMoments`` does; ``cells_nonempty`` and ``longest_run`` are then the largest of the
+    ranks' own."""
+    md._sync_stream()
+    edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+    ngroups = int(edges.size) - 1
+    words = int(md.lib.jb_spectrum_words(md.handle, ngroups))
+    if words == 0:
+        raise ValueError(f"EvaluateRadiationSpectrum: {edges.size} edges; "
+                         f"2 .. {_lib.JB_SPECTRUM_MAX_GROUPS + 1} are allowed")
+    nx = md.mesh.nx
+    shape = (ngroups + 2, md.nblocks, int(nx[2]), int(nx[1]), int(nx[0]))
+    if md.spectrum is None or tuple(md.spectrum.shape) != shape:
+        md.spectrum = torch.empty(shape, dtype=torch.float64, device=md.device)
+    assert md.spectrum.numel() == words
+    rep = _lib.SpectrumReport()
+    _lib.check(md.lib.jb_evaluate_radiation_spectrum(md.pkg.ctx, md.handle, C.byref(md.sv), edges.ctypes.data, ngroups,
+                                                     md.spectrum.data_ptr(), C.byref(rep)))
+    report = rep.as_dict()
+    if md.replicated:
+        md.comm.allreduce_sum_tensor(md.spectrum)
+        keys = ("n_counted", "n_skipped", "n_below", "n_above")
+        total = md.comm.allreduce_sum_int64(np.array([report[k] for k in keys], dtype=np.int64))
+        report.update({k: int(v) for k, v in zip(keys, total)})
+        for k in ("cells_nonempty", "longest_run"):                # (below 2^53: exact as floats)
+            report[k] = int(md.comm.allreduce_max_float(float(report[k])))
+    md.spectrum_report = report
+    return md.spectrum, report
 
 
 def UpdateFluid(md: MeshData) -> TaskStatus:
